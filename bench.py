@@ -11,8 +11,12 @@ cached between steps.
 Strong scaling (BASELINE C4: ONE 40000^2 raster, tiles sharded over the GPUs): with N ranks the 79 tile rows are
 split 10/10/.../9 and `value` is the whole raster's pixels / the max-over-ranks step time.
 
-Also reported (DESIGN.md "Measurement"):
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the result line;
+--dump-outputs DIR also writes what the last timed step returned (dump_outputs).  Reported from the timed steps
+themselves (DESIGN.md "Measurement"):
   roofline      dominant kernel's algorithmic bytes / its HIP-event-timed average duration vs 8 TB/s
+With --full, the legs that take runs of their own follow the timed steps:
+  allgather_us  (N > 1) the size all-gather inside the steps and isolated after a barrier
   bbox_extract  C5: 1000 seed-7 bbox queries against the streaming data in HBM (selection + fused decode +
                 de-normalisation stored straight into page-locked host memory); at N > 1 each rank answers the
                 queries whose tile it holds
@@ -62,6 +66,11 @@ def parse():
     ap.add_argument("--width", type=int, default=40000)
     ap.add_argument("--bands", type=int, default=4)
     ap.add_argument("--tile", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the other legs: C5 bbox extract, the isolated all-gather "
+                         "(N > 1), the N = 1 extras and the CPU baseline (the options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-tiles", type=int, default=632, help="tiles in the CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=1)
     ap.add_argument("--no-cpu", action="store_true")
@@ -192,7 +201,8 @@ def main():
         "dtype": "int16",
         "data": "synthetic (on-device DEM recipe of SURVEY.md 8d, seed 1234)",
         "config": {"workload": ("C4 " if (H, W, B, T) == (40000, 40000, 4, 512) else "") +
-                   "create-streaming encode (band 1, device-resident) + C5 bbox extract",
+                   "create-streaming encode (band 1, device-resident)" +
+                   (" + C5 bbox extract" if args.full and args.queries > 0 else ""),
                    "raster": f"{H}x{W}x{B} int16", "tile_size": T, "tiles": trows * tcols,
                    "tiles_rank0": int(counts[0]), "blocksize": 4096, "compression_level": 5,
                    "parallelism": parallelism(world, backend),
@@ -213,7 +223,8 @@ def main():
                      "step_traffic": step_traffic_for(args.traffic_json, px_rank, ms_per_step)},
     }
     if comm is not None:
-        result["allgather_us"] = allgather_figures(comm, ag_s, np.diff(off), counts)
+        if args.full:
+            result["allgather_us"] = allgather_figures(comm, ag_s, np.diff(off), counts)
         result["config"]["compressed_bytes_total"] = int(comm.allgather_i64(np.array([comp_bytes])).sum())
     else:
         result["config"]["compressed_bytes_total"] = comp_bytes
@@ -225,6 +236,23 @@ def main():
                                        "frac": round(rate / VALU_PEAK_GINST_S, 4)}
 
     progress(f"step {ms_per_step:.3f} ms")
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), arena, off, mn, mx, rank)
+    if args.full:
+        full_legs(args, ctx, comm, raster, arena, off, mn, mx, row0, rows, counts, result)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    arena.close()
+    raster.close()
+    if comm is not None:
+        comm.close()
+    ctx.close()
+
+
+def full_legs(args, ctx, comm, raster, arena, off, mn, mx, row0, rows, counts, result):
+    """--full: the legs beside the headline figure, each a run of its own after the timed steps, added to `result`."""
+    T, W, H = args.tile, args.width, args.height
+    rank, world = (comm.rank, comm.world) if comm is not None else (0, 1)
     if args.queries > 0:
         progress("bbox_extract")
         bx = bbox_extract(ctx, comm, raster, arena, off, mn, mx, H, W, T, row0, counts, args.queries)
@@ -244,13 +272,35 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu:  # (the CPU baseline is an N = 1 figure)
         progress("cpu_baseline")
         result["cpu_baseline"] = cpu_baseline(ctx, raster, rows, W, T, off, arena, args)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    arena.close()
-    raster.close()
-    if comm is not None:
-        comm.close()
-    ctx.close()
+
+
+def dump_outputs(outdir, arena, off, tmin, tmax, rank, sample_tiles=16, sample_bytes=512 << 10, chunk=256 << 20):
+    """--dump-outputs: what the last timed step handed its caller, as float64 / float32 .npy files under `outdir`
+    (rank r > 0 of an N > 1 run writes <name>_rank<r>.npy).  The inputs are seeded, so two builds given the same
+    arguments can be compared file by file.
+      tile_off, tile_min, tile_max  the step's return values (byte offset of every tile's frames in the arena, one
+                                    more entry than tiles; per-tile minimum and maximum), float64
+      tile_bytesum                  per tile, the sum of its frame bytes in the arena (every byte counted), float64
+      frames_sample                 the frame bytes themselves (float32) of `sample_tiles` tiles drawn with a fixed
+                                    seed, at most `sample_bytes` from the start of each: 32 MiB at the most"""
+    outdir.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    n = len(off) - 1
+    np.save(outdir / f"tile_off{sfx}.npy", np.asarray(off, dtype=np.float64))
+    np.save(outdir / f"tile_min{sfx}.npy", np.asarray(tmin, dtype=np.float64))
+    np.save(outdir / f"tile_max{sfx}.npy", np.asarray(tmax, dtype=np.float64))
+    sums = np.zeros(n, dtype=np.float64)
+    i = 0
+    while i < n:  # the arena comes to the host in groups of whole tiles of at most `chunk` bytes (or one tile)
+        j = min(n, max(i + 1, int(np.searchsorted(off, off[i] + chunk, side="right")) - 1))
+        part = arena.download(int(off[j] - off[i]), int(off[i]))
+        sums[i:j] = np.add.reduceat(part, off[i:j] - off[i], dtype=np.int64)  # (no tile's frames are empty)
+        i = j
+    np.save(outdir / f"tile_bytesum{sfx}.npy", sums)
+    picks = np.sort(np.random.default_rng(20240607).choice(n, size=min(sample_tiles, n), replace=False)) if n else []
+    parts = [arena.download(int(min(off[t + 1] - off[t], sample_bytes)), int(off[t])) for t in picks]
+    sample = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    np.save(outdir / f"frames_sample{sfx}.npy", sample.astype(np.float32))
 
 
 def progress(what):

@@ -3,8 +3,9 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
-mkdir -p gpurun_out/check
-timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/check/smoke.log 2>&1 || exit 1
-timeout -k 10 600 python -u -m pytest tests -x -v -m gpu --timeout 120 --timeout-method thread > gpurun_out/check/pytest.log 2>&1 || exit 1
-timeout -k 10 600 python -u bench.py --steps 5 --warmup 2 --no-cpu > gpurun_out/check/bench.log 2>&1 || exit 1
+O=${FRS_OUT:-$PWD/bench_out}/check
+mkdir -p $O
+timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1
+timeout -k 10 600 python -u -m pytest tests -x -v -m gpu --timeout 120 --timeout-method thread > $O/pytest.log 2>&1 || exit 1
+timeout -k 10 600 python -u bench.py --full --steps 5 --warmup 2 --no-cpu > $O/bench.log 2>&1 || exit 1
 echo done
