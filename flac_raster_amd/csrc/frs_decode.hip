@@ -1716,7 +1716,8 @@ __device__ __attribute__((always_inline)) inline void decode_one_frame(const uin
             // which for sbps + shift <= 31 leaves the sbps range -- the restore checks every sample and redoes the
             // subframe on the exact 64-bit path if one is out (never on a stream libFLAC decodes in 32 bits)
             const bool wrap_checked = !safe32 && sbps <= 17 && sbps + shift <= 31;
-            const bool narrow = sbps <= 23 && (safe32 || wrap_checked);
+            // (the fast path restores on an 8-tap register ring: orders 9..32 take the exact loop below)
+            const bool narrow = o <= 8 && sbps <= 23 && (safe32 || wrap_checked);
             bool done = false;
             if (resbuf && narrow && bs <= kDecResMax) {
                 const auto br0 = br;

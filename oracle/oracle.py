@@ -148,9 +148,10 @@ def frame_assignments(data: bytes, channels: int, bps: int, max_samples: int) ->
     return ca[: -(-r // 4096) if r else 0].copy()
 
 
-def subframe_types(data: bytes, channels: int, bps: int, max_samples: int) -> np.ndarray:
+def subframe_types(data: bytes, channels: int, bps: int, max_samples: int, blocksize: int = 4096) -> np.ndarray:
     """(type code, residual partition order) of every subframe, frame-major: type 0 CONSTANT, 1 VERBATIM,
-    8 + order FIXED, 31 + order LPC; partition order -1 for CONSTANT / VERBATIM."""
+    8 + order FIXED, 31 + order LPC; partition order -1 for CONSTANT / VERBATIM.  blocksize (>= 16): the samples of
+    every frame but the last."""
     buf = np.frombuffer(data, dtype=np.uint8)
     out = np.empty((max_samples, channels), dtype=np.int32)
     cap = (max_samples // 16 + 16) * channels
@@ -158,7 +159,7 @@ def subframe_types(data: bytes, channels: int, bps: int, max_samples: int) -> np
     r = lib().orc_decode_frames_sf(_ptr(buf), len(buf), channels, bps, _ptr(out), max_samples, _ptr(sf), cap)
     if r < 0:
         raise RuntimeError(f"oracle decode error {r}")
-    sf = sf[: (-(-r // 4096) if r else 0) * channels]
+    sf = sf[: (-(-r // blocksize) if r else 0) * channels]
     t = sf & 0xFF
     po = np.where((t >= 8), sf >> 8, -1)
     return np.stack([t, po], axis=1)

@@ -6,8 +6,11 @@ k_analyze_lpc_hi's per-window LPC candidates of the subdivide_tukey apodizations
 order 6; at 1 / 4 on two channels loose mid/side: a leader pass per group of frames, then the coding pass); the fast
 kernels hard-code level 5's search and are not selected.  Covered: mono, two channels (independent at 0 / 3,
 exhaustive mid/side at 2 / 5 / 6..8, loose at 1 / 4), three channels, a 32-bit stream, the spatial {-1, 0, 1} mode,
-partial last frames, the file-level convert / convert --spatial paths, and the level range check.
+partial last frames, the file-level convert / convert --spatial paths, the level range check, and the decode of
+streams of levels 0..8 by every decoder kind (levels 7 / 8 emit LPC orders 9..12, which level 5 never does).
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -16,6 +19,7 @@ from flac_raster_amd.converter import RasterFLACConverter
 from flac_raster_amd.spatial_encoder import SpatialFLACEncoder
 from oracle import oracle as O
 from oracle import pipeline as P
+from tests.test_gpu_decode import DECODERS, _decoder_ctx
 from tests.test_levels import _ok_levels, level_signal
 
 pytestmark = pytest.mark.gpu
@@ -129,3 +133,66 @@ def test_high_levels_and_loose_stereo_long_streams(gpu_ctx):
                               compression_level=lv)
         arena, off, mn, mx, bps = gpu_ctx.encode_tiles_host(arr, d)
         assert arena[:off[-1]].tobytes() == O.encode_frames(pcm, obps, 44100, level=lv), lv
+
+
+# ---------------------------------------------------------------------------------- decode of every level's streams
+_DEC_FRAMES = 66  # >= 64: the multi-channel lane path takes the stream
+
+
+@functools.lru_cache(maxsize=None)
+def _level_stream(ch, lv):
+    """(pcm [n, ch] int32, oracle frames at level lv): smooth 16-bit bands (levels 7 / 8 choose LPC orders 9..12 on
+    them); the last band has 2 wasted bits, a mono stream from its middle frame on."""
+    n = _DEC_FRAMES * 4096
+    rng = np.random.default_rng(90 + ch)
+    t = np.arange(n)
+    cols = [900 + 3000 * np.sin(t / (61.0 + 17 * c)) * np.cos(t / 977.0) + 700 * np.sin(t / 5.3 + c)
+            + 20 * rng.random(n) for c in range(ch)]
+    x = np.stack(cols, axis=1).astype(np.int32)
+    x[n // 2 if ch == 1 else 0:, ch - 1] &= ~3
+    x.setflags(write=False)
+    return x, O.encode_frames(x, 16, 44100, level=lv)
+
+
+def test_high_level_streams_hold_the_layouts_under_test():
+    """Level 8 codes these bands with LPC orders above 8, with and without the wasted bits (a CPU property of the
+    oracle's encoder, asserted here so the decode cases below cannot lose their subject unnoticed)."""
+    for ch in (1, 2, 3):
+        x, fr = _level_stream(ch, 8)
+        t = O.subframe_types(fr, ch, 16, len(x))[:, 0].reshape(-1, ch)
+        assert (t[:, ch - 1] > 39).any(), ch          # on the band with wasted bits (sbps 14)
+        assert (t[: _DEC_FRAMES // 2, 0] > 39).any(), ch  # and on one without
+
+
+@pytest.mark.parametrize("ch,lv,kind", [(1, lv, k) for lv in (0, 3, 6, 8) for k in DECODERS]
+                         + [(2, lv, k) for lv in (1, 4, 8) for k in ("lane", "wave")]
+                         + [(3, 8, k) for k in ("lane", "wave")])
+def test_level_streams_decode_to_their_pcm(ch, lv, kind, monkeypatch):
+    """Streams of levels other than 5 (convert -c N) through the GPU decoders: the PCM that went in comes out.
+    Mono on all four decoder kinds; two and three bands on the multi-channel lane path and the wave decoder (the
+    pipe settings send multi-channel streams to the wave decoder too)."""
+    x, fr = _level_stream(ch, lv)
+    blob = np.frombuffer(fr, dtype=np.uint8)
+    dctx = _decoder_ctx(kind, monkeypatch)
+    try:
+        got = dctx.decode_frames_host(blob, [0, blob.size], [len(x)], channels=ch, bps=16).reshape(-1, ch)
+        bad = np.flatnonzero((got != x).any(1))
+        assert bad.size == 0, (bad.size, "samples differ; frames", np.unique(bad // 4096).tolist())
+    finally:
+        dctx.close()
+
+
+def test_level8_file_round_trip_three_bands(gpu_ctx, tmp_path):
+    """tiff_to_flac(compression_level=8) -> flac_to_tiff of a 300 x 701 3-band raster returns the input."""
+    rng = np.random.default_rng(77)
+    H, W = 300, 701
+    y, x = np.meshgrid(np.linspace(0, 20, H), np.linspace(0, 20, W), indexing="ij")
+    arr = np.stack([900 + 300 * np.sin(x * (0.5 + 0.1 * b)) * np.cos(y * 0.3) + 40 * rng.random((H, W))
+                    for b in range(3)]).astype(np.int16)
+    arr[2] &= ~3
+    src, out, back = tmp_path / "rgb.tif", tmp_path / "rgb_c8.flac", tmp_path / "rgb_back.tif"
+    geotiff.write(src, arr, geotiff.Affine(10.0, 0.0, 500000.0, 0.0, -10.0, 4000000.0), 32636)
+    conv = RasterFLACConverter(gpu_ctx)
+    conv.tiff_to_flac(src, out, compression_level=8)
+    conv.flac_to_tiff(out, back)
+    assert np.array_equal(geotiff.read(back).data, arr)
