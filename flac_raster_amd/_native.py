@@ -37,7 +37,21 @@ EXPORTS = (
     "frs_dev_malloc", "frs_dev_free", "frs_host_malloc", "frs_host_free", "frs_memcpy_h2d", "frs_memcpy_d2h", "frs_ctx_sync",
     "frs_synth_raster_device", "frs_ctx_stream", "frs_profile_enable", "frs_profile_avg_ms",
     "frs_profile_reset", "frs_comm_unique_id", "frs_comm_init", "frs_comm_destroy", "frs_comm_allgather_i64",
+    "frs_compare_device", "frs_compare",
 )
+
+# launch constants of k_compare (csrc/frs_compare.hip: kCmpBlock, kCmpUnroll, kCmpMaxGroups): a work-group step covers
+# COMPARE_BLOCK * COMPARE_UNROLL 16-byte vectors of each raster, and a band gets one work-group per step up to
+# COMPARE_MAX_GROUPS // nbands, grid-striding beyond that
+COMPARE_BLOCK = 256
+COMPARE_UNROLL = 4
+COMPARE_MAX_GROUPS = 2048
+
+
+def compare_groups(count: int, nbands: int, itemsize: int) -> int:
+    """Work-groups per band of a compare of `count` elements per band (compare_groups in csrc/frs_compare.hip)."""
+    chunk = COMPARE_BLOCK * COMPARE_UNROLL * (16 // itemsize)
+    return max(1, min(-(-count // chunk), max(1, COMPARE_MAX_GROUPS // nbands)))
 
 
 class NativeUnavailable(RuntimeError):
@@ -62,6 +76,29 @@ class EncodeDesc(ctypes.Structure):
         ("norm_mode", ctypes.c_int32),
         ("tile_begin", ctypes.c_int64), ("tile_end", ctypes.c_int64),
     ]
+
+
+class CompareDesc(ctypes.Structure):
+    """frs_compare_desc"""
+    _fields_ = [
+        ("height", ctypes.c_int64), ("width", ctypes.c_int64),
+        ("nbands", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("a_row_stride", ctypes.c_int64), ("a_band_stride", ctypes.c_int64),
+        ("b_row_stride", ctypes.c_int64), ("b_band_stride", ctypes.c_int64),
+    ]
+
+
+class CompareBand(ctypes.Structure):
+    """frs_compare_band"""
+    _fields_ = [
+        ("count", ctypes.c_int64), ("n_diff", ctypes.c_int64), ("first_diff", ctypes.c_int64),
+        ("a_min", ctypes.c_double), ("a_max", ctypes.c_double), ("b_min", ctypes.c_double),
+        ("b_max", ctypes.c_double), ("np_max_abs", ctypes.c_double), ("np_sum_abs", ctypes.c_double),
+        ("np_sum_sq", ctypes.c_double), ("max_abs", ctypes.c_double), ("sum_abs", ctypes.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 _lib = None
@@ -151,6 +188,11 @@ def load_library(path: Optional[os.PathLike] = None):
         L.frs_comm_destroy.argtypes = [vp]
         L.frs_comm_allgather_i64.restype = i32
         L.frs_comm_allgather_i64.argtypes = [vp, ip64, i64, ip64]
+        cmp_args = [ctxp, ctypes.POINTER(CompareDesc), vp, vp, ctypes.POINTER(CompareBand)]
+        L.frs_compare_device.restype = i32
+        L.frs_compare_device.argtypes = cmp_args
+        L.frs_compare.restype = i32
+        L.frs_compare.argtypes = cmp_args
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -179,6 +221,20 @@ def _is_window_of(raster, desc) -> bool:
     if st[-2] // es != desc.row_stride or raster.shape[-1] != desc.width or raster.shape[-2] != desc.height:
         return False
     return raster.ndim == 2 or (st[0] // es == desc.band_stride and raster.shape[0] >= desc.band0 + desc.nbands)
+
+
+def _window_layout(r: np.ndarray):
+    """(array, row_stride, band_stride) to hand a (bands, h, w) or (h, w) raster to frs_compare: the array itself with
+    its element strides when it is C-contiguous or a window view of a larger raster (unit column stride, positive row
+    and band strides that are whole elements, rows not overlapping), else a contiguous copy."""
+    es = r.dtype.itemsize
+    st = r.strides
+    h, w = r.shape[-2], r.shape[-1]
+    ok = st[-1] == es and all(x > 0 and x % es == 0 for x in st) and st[-2] // es >= w
+    if not ok or r.flags.c_contiguous:
+        r = np.ascontiguousarray(r)
+        return r, w, h * w
+    return r, st[-2] // es, (st[0] // es if r.ndim == 3 else (st[-2] // es) * h)
 
 
 class DeviceBuffer:
@@ -469,6 +525,47 @@ class Context:
         self._check(self.lib.frs_denormalize_device(self.handle, ctypes.c_void_p(pcm_ptr), int(n), int(pcm_bps),
                                                     float(data_min), float(data_max), DTYPE_CODES[np.dtype(dtype)],
                                                     ctypes.c_void_p(out_ptr)))
+
+    # ---- compare
+    @staticmethod
+    def make_compare_desc(height, width, dtype, *, nbands=1, a_row_stride=None, a_band_stride=None,
+                          b_row_stride=None, b_band_stride=None) -> CompareDesc:
+        d = CompareDesc()
+        d.height, d.width, d.nbands = int(height), int(width), int(nbands)
+        d.dtype = DTYPE_CODES[np.dtype(dtype)]
+        d.a_row_stride = int(width if a_row_stride is None else a_row_stride)
+        d.b_row_stride = int(width if b_row_stride is None else b_row_stride)
+        d.a_band_stride = int(d.a_row_stride * d.height if a_band_stride is None else a_band_stride)
+        d.b_band_stride = int(d.b_row_stride * d.height if b_band_stride is None else b_band_stride)
+        return d
+
+    def compare_host(self, a: np.ndarray, b: np.ndarray, as_dicts: bool = True):
+        """Difference statistics of two host rasters ((bands, h, w) or (h, w), same shape and dtype): one
+        frs_compare_band per band, as dicts (or the CompareBand structures).  A strided window view of a larger
+        raster is passed by its origin pointer and strides (as _is_window_of for the encoder); anything else that is
+        not C-contiguous is copied first."""
+        a, b = np.asarray(a), np.asarray(b)
+        if a.shape != b.shape or a.dtype != b.dtype or a.ndim not in (2, 3):
+            raise ValueError("compare_host needs two (bands, h, w) or (h, w) arrays of one shape and dtype")
+        if a.dtype not in DTYPE_CODES:
+            raise ValueError(f"unsupported dtype {a.dtype}")
+        if a.size == 0:
+            raise ValueError("empty raster")
+        a, ars, abs_ = _window_layout(a)
+        b, brs, bbs = _window_layout(b)
+        nb = a.shape[0] if a.ndim == 3 else 1
+        d = self.make_compare_desc(a.shape[-2], a.shape[-1], a.dtype, nbands=nb, a_row_stride=ars, a_band_stride=abs_,
+                                   b_row_stride=brs, b_band_stride=bbs)
+        out = (CompareBand * nb)()
+        self._check(self.lib.frs_compare(self.handle, ctypes.byref(d), _p(a), _p(b), out))
+        return [x.as_dict() for x in out] if as_dicts else list(out)
+
+    def compare_device(self, a_ptr: int, b_ptr: int, desc: CompareDesc, as_dicts: bool = True):
+        """frs_compare_device on two device rasters laid out as `desc` says."""
+        out = (CompareBand * max(int(desc.nbands), 1))()
+        self._check(self.lib.frs_compare_device(self.handle, ctypes.byref(desc), ctypes.c_void_p(a_ptr),
+                                                ctypes.c_void_p(b_ptr), out))
+        return [x.as_dict() for x in out] if as_dicts else list(out)
 
     # ---- bench helpers
     def synth_raster(self, buf: DeviceBuffer, bands: int, height: int, width: int, row0: int = 0,

@@ -26,11 +26,18 @@ def convert(
     verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose logging"),
     spatial_tiling: bool = typer.Option(False, "--spatial", "-s", help="Enable spatial tiling for HTTP range streaming"),
     tile_size: int = typer.Option(512, "--tile-size", help="Size of spatial tiles (default: 512x512)"),
+    verify: bool = typer.Option(False, "--verify", help="Extension: decode the written FLAC and compare it with the "
+                                                        "source raster on the GPU (plain TIFF to FLAC only); exit "
+                                                        "status 3 when it differs"),
 ):
     """Convert between TIFF and FLAC formats"""
     from .converter import RasterFLACConverter
     if verbose:
         logging.getLogger("flac_raster").setLevel(logging.DEBUG)
+    # --verify is checked before anything else is looked at or done
+    if verify and (spatial_tiling or input_file.suffix.lower() not in (".tif", ".tiff")):
+        typer.echo("Error: --verify applies to plain TIFF to FLAC conversion", err=True)
+        raise typer.Exit(1)
     if not input_file.exists():
         typer.echo(f"Error: Input file does not exist: {input_file}", err=True)
         raise typer.Exit(1)
@@ -46,6 +53,7 @@ def convert(
     if output_file.exists() and not force:
         typer.echo(f"Error: Output file already exists: {output_file}", err=True)
         raise typer.Exit(1)
+    differs = False
     try:
         conv = RasterFLACConverter()
         if kind == "tiff_to_flac":
@@ -55,10 +63,23 @@ def convert(
         else:
             conv.flac_to_tiff(input_file, output_file)
         typer.echo(f"SUCCESS: {output_file}")
+        if verify:
+            from . import geotiff
+            from .compare import compare_arrays
+            back, _ = conv.decode_bytes(output_file.read_bytes())
+            ex = compare_arrays(geotiff.read(input_file).data, back, ctx=conv.ctx, show_bands=False)["exact"]
+            differs = ex["n_different"] != 0
+            if differs:
+                typer.echo(f"VERIFY: differs (n_different={ex['n_different']}, "
+                           f"max_difference={ex['max_difference']})")
+            else:
+                typer.echo("VERIFY: lossless")
     except Exception as e:  # reference: any error -> exit 1 (cli.py:90-93)
         log.exception("Conversion failed")
         typer.echo(f"Error during conversion: {e}", err=True)
         raise typer.Exit(1)
+    if differs:
+        raise typer.Exit(3)
 
 
 @app.command("create-streaming")
@@ -264,6 +285,38 @@ def info(file_path: str = typer.Argument(..., help="FLAC or TIFF file to inspect
             con.print("\n[yellow]No embedded or sidecar metadata found[/yellow]")
     else:
         con.print(f"[red]Error: Unsupported file format: {suffix}[/red]")
+        raise typer.Exit(1)
+
+
+@app.command()
+def compare(
+    file1: Path = typer.Argument(..., help="First TIFF file"),
+    file2: Path = typer.Argument(..., help="Second TIFF file"),
+    show_bands: bool = typer.Option(True, "--show-bands/--no-bands", help="Show per-band statistics"),
+    export_json: Optional[Path] = typer.Option(None, "--export", "-e", help="Export comparison results to JSON"),
+):
+    """Compare two TIFF files and display statistics"""  # reference cli.py:247-290
+    from rich.console import Console
+    con = Console()
+    for f in (file1, file2):
+        if not f.exists():
+            con.print(f"[red]Error: File does not exist: {f}[/red]")
+            raise typer.Exit(1)
+    for f in (file1, file2):
+        if f.suffix.lower() not in (".tif", ".tiff"):
+            con.print(f"[red]Error: {f} is not a TIFF file[/red]")
+            raise typer.Exit(1)
+    try:
+        from .compare import compare_tiffs, display_comparison_table
+        results = compare_tiffs(file1, file2, show_bands)
+        display_comparison_table(results, con)
+        if export_json:
+            with open(export_json, "w") as fh:
+                json.dump(results, fh, indent=2)
+            con.print(f"\n[green]SUCCESS: Comparison results exported to: {export_json}[/green]")
+    except Exception as e:
+        log.exception("Comparison failed")
+        con.print(f"[red]Error during comparison: {e}[/red]")
         raise typer.Exit(1)
 
 

@@ -125,9 +125,10 @@ void frs_ctx_destroy(frs_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->tiles, &ctx->norms, &ctx->analysis, &ctx->slots, &ctx->frame_bytes, &ctx->frame_off,
                       &ctx->window, &ctx->tile_sizes, &ctx->luts, &ctx->status, &ctx->frame_tile, &ctx->hdr_tab, &ctx->wave_tab, &ctx->plist, &ctx->lpc_cand, &ctx->sub_est, &ctx->st_pick, &ctx->window_hi, &ctx->loose_assign, &ctx->loose_lead, &ctx->sub_slots, &ctx->sub_bits, &ctx->mc_bytes, &ctx->raster_stage, &ctx->arena_stage, &ctx->host_pack,
                       &ctx->dec_cand, &ctx->dec_count, &ctx->dec_pcm, &ctx->dec_soff, &ctx->dec_next, &ctx->dec_status, &ctx->dec_fb, &ctx->dec_sel, &ctx->dec_crc,
-                      &ctx->dec_chass};
+                      &ctx->dec_chass, &ctx->cmp_part, &ctx->cmp_stage};
     for (DevBuf *b : bufs) b->release();
     ctx->pin.release();
+    ctx->cmp_pin.release();
     ctx->ring[0].release();
     ctx->ring[1].release();
     if (ctx->h2d_stream) hipStreamDestroy(ctx->h2d_stream);
@@ -597,6 +598,67 @@ int frs_synth_raster_device(frs_ctx *ctx, int16_t *dev, int32_t bands, int64_t h
     }
     FRS_HIP(hipSetDevice(ctx->device));
     return frs::synth_job(ctx, dev, bands, height, width, row0, full_height, seed);
+}
+
+}  // extern "C"
+
+// elements from a raster's origin to the end of its last row, or -1 when that does not fit 63 bits
+static int64_t compare_extent(int64_t h, int64_t w, int64_t nb, int64_t rs, int64_t bs) {
+    int64_t x, y;
+    if (__builtin_mul_overflow(nb - 1, bs, &x) || __builtin_mul_overflow(h - 1, rs, &y) ||
+        __builtin_add_overflow(x, y, &x) || __builtin_add_overflow(x, w, &x) || x > (INT64_MAX >> 4))
+        return -1;
+    return x;
+}
+
+static int check_compare_desc(frs_ctx *ctx, const frs_compare_desc *d) {
+    if (!d) { ctx->err = "null desc"; return FRS_E_ARG; }
+    if (d->height < 1 || d->width < 1 || d->nbands < 1) { ctx->err = "bad geometry"; return FRS_E_ARG; }
+    if (d->nbands > 65535) { ctx->err = "compare: at most 65535 bands (one grid row each)"; return FRS_E_ARG; }
+    if (d->a_row_stride < d->width || d->b_row_stride < d->width) { ctx->err = "row_stride < width"; return FRS_E_ARG; }
+    if (frs::dtype_size(d->dtype) == 0) { ctx->err = "bad dtype"; return FRS_E_ARG; }
+    if (d->nbands > 1 && (d->a_band_stride < 0 || d->b_band_stride < 0)) { ctx->err = "negative band_stride"; return FRS_E_ARG; }
+    int64_t count;
+    if (__builtin_mul_overflow(d->height, d->width, &count) ||
+        compare_extent(d->height, d->width, d->nbands, d->a_row_stride, d->a_band_stride) < 0 ||
+        compare_extent(d->height, d->width, d->nbands, d->b_row_stride, d->b_band_stride) < 0) {
+        ctx->err = "compare: raster extent overflows";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
+extern "C" {
+
+int frs_compare_device(frs_ctx *ctx, const frs_compare_desc *desc, const void *a_dev, const void *b_dev,
+                       frs_compare_band *out_host) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_compare_desc(ctx, desc)) return rc;
+    const uintptr_t es = (uintptr_t)frs::dtype_size(desc->dtype);
+    if (!a_dev || !b_dev || !out_host || reinterpret_cast<uintptr_t>(a_dev) % es || reinterpret_cast<uintptr_t>(b_dev) % es) {
+        ctx->err = "compare: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    FRS_HIP(hipSetDevice(ctx->device));
+    return frs::compare_job(ctx, desc, a_dev, b_dev, out_host);
+}
+
+int frs_compare(frs_ctx *ctx, const frs_compare_desc *desc, const void *a_host, const void *b_host,
+                frs_compare_band *out_host) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_compare_desc(ctx, desc)) return rc;
+    if (!a_host || !b_host || !out_host) { ctx->err = "null pointer"; return FRS_E_ARG; }
+    FRS_HIP(hipSetDevice(ctx->device));
+    const size_t es = (size_t)frs::dtype_size(desc->dtype);
+    const size_t na = (size_t)compare_extent(desc->height, desc->width, desc->nbands, desc->a_row_stride, desc->a_band_stride) * es;
+    const size_t nb = (size_t)compare_extent(desc->height, desc->width, desc->nbands, desc->b_row_stride, desc->b_band_stride) * es;
+    FRS_HIP(ctx->raster_stage.ensure(na));
+    FRS_HIP(ctx->cmp_stage.ensure(nb));
+    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, a_host, na, hipMemcpyHostToDevice, ctx->stream));
+    FRS_HIP(hipMemcpyAsync(ctx->cmp_stage.ptr, b_host, nb, hipMemcpyHostToDevice, ctx->stream));
+    return frs::compare_job(ctx, desc, ctx->raster_stage.ptr, ctx->cmp_stage.ptr, out_host);
 }
 
 }  // extern "C"

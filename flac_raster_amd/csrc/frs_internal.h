@@ -104,6 +104,9 @@ struct frs_ctx {
     int window_hi_bs = 0, window_hi_parts = 0;
     DevBuf sub_est, st_pick;  // two-channel fast path: subframe estimates (L, R, M, S), the assignment per frame
     DevBuf zero_sub;          // raw-frames tiles: all-zero subframe flags (k_zero_subframes)
+    // compare (frs_compare*): per-work-group partial records, their pinned host copy, the second raster's staging
+    DevBuf cmp_part, cmp_stage;
+    HostPin cmp_pin;
     // page-locked host allocations of this context (frs_host_malloc): a C5 decode whose output lies in one returns
     // when the kernel's last work-group has published it, before the stream's completion signal (`unsynced` then
     // makes the next call check the stream for an asynchronous fault first)
@@ -159,4 +162,6 @@ int64_t arena_bound(const frs_encode_desc *d);
 int synth_job(frs_ctx *ctx, int16_t *dev, int bands, int64_t height, int64_t width, int64_t row0, int64_t full_height,
               uint64_t seed);
 int dtype_size(int dt);
+// Difference statistics of two device rasters (frs_compare.hip); the descriptor is already validated.
+int compare_job(frs_ctx *ctx, const frs_compare_desc *d, const void *a_dev, const void *b_dev, frs_compare_band *out);
 }  // namespace frs

@@ -167,6 +167,41 @@ int frs_denormalize_device(frs_ctx *ctx, const int32_t *pcm_dev, int64_t n, int3
 int frs_denormalize(frs_ctx *ctx, const int32_t *pcm_host, int64_t n, int32_t pcm_bps, double data_min,
                     double data_max, int32_t out_dtype, void *out_host);
 
+/* Difference statistics of two rasters in one pass over both: replaces compare.py:55-78 (np.array_equal,
+ * np.max(np.abs(a-b)), np.mean(np.abs(a-b)), np.sqrt(np.mean((a-b)**2)), np.min/np.max of each file, overall and
+ * per band).  A and B are [nbands][height][width] elements of the same dtype, each with its own row / band stride
+ * (elements), so a window of a larger raster can be compared.  out_host has nbands entries:
+ *   count                    height*width
+ *   n_diff, first_diff       elements with a != b (C: NaN differs from everything, -0.0 == 0.0) and the smallest
+ *                            row*width+col among them, or -1
+ *   a_min .. b_max           as double; NaN when the band holds a NaN (numpy's min/max propagate it)
+ *   np_max_abs, np_sum_abs,  what numpy computes IN THE DTYPE, wraps included: integer a-b wraps (uint8: 5-10 = 251),
+ *   np_sum_sq                abs of a signed value wraps (abs(int16(-32768)) = -32768), unsigned abs is the identity,
+ *                            an integer square wraps (int16: 300*300 -> 24464); float terms are formed in the dtype
+ *                            (the square is a separate rounded product).  np_max_abs is NaN when a difference is NaN.
+ *                            mean = np_sum_abs/count and rmse = sqrt(np_sum_sq/count) are numpy's values.
+ *   max_abs, sum_abs         the true |a-b| without wrap (int64 for integer dtypes, double for floats)
+ * Integer sums are exact (64-bit partials added in 128 bits, converted to double once); float terms are accumulated
+ * in double in a fixed order that depends only on shape and dtype, so results reproduce bit for bit.  Dense or
+ * 16-byte-aligned-row inputs run on 16-byte loads; any other layout is read element by element (slower, same
+ * result).  FRS_E_ARG: height, width or nbands < 1, nbands > 65535, a row stride < width, unknown dtype, a pointer not
+ * aligned to the element size, or a shape whose 64-bit partial sums could overflow (more than 2^30 elements per
+ * work-group: beyond ~2^41 elements per band).  frs_compare copies (nbands-1)*band_stride + (height-1)*row_stride +
+ * width elements of each raster through the context's staging buffers.  Both are synchronous on the context stream. */
+typedef struct {
+    int64_t height, width;
+    int32_t nbands, dtype;      /* dtype: enum frs_dtype */
+    int64_t a_row_stride, a_band_stride, b_row_stride, b_band_stride;
+} frs_compare_desc;
+typedef struct {
+    int64_t count, n_diff, first_diff;
+    double a_min, a_max, b_min, b_max, np_max_abs, np_sum_abs, np_sum_sq, max_abs, sum_abs;
+} frs_compare_band;
+int frs_compare_device(frs_ctx *ctx, const frs_compare_desc *desc, const void *a_dev, const void *b_dev,
+                       frs_compare_band *out_host);
+int frs_compare(frs_ctx *ctx, const frs_compare_desc *desc, const void *a_host, const void *b_host,
+                frs_compare_band *out_host);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
@@ -206,7 +241,7 @@ int frs_synth_raster_device(frs_ctx *ctx, int16_t *dev, int32_t bands, int64_t h
 void *frs_ctx_stream(frs_ctx *ctx);
 /* Average device time (ms) of the named kernel over the launches since the last reset, measured with
  * HIP events on the context stream (kernel: "encode" = the frame-encode kernel, "analyze", "stats",
- * "compact", "decode"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
+ * "compact", "decode", "compare"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
 int frs_profile_enable(frs_ctx *ctx, int on);
 double frs_profile_avg_ms(frs_ctx *ctx, const char *kernel);
 void frs_profile_reset(frs_ctx *ctx);
