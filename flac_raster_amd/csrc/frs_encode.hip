@@ -2598,6 +2598,8 @@ template <int STEP> __device__ inline uint64_t bfly_partner64(uint64_t v) {
     return ((uint64_t)bfly_partner<STEP>((uint32_t)(v >> 32)) << 32) | bfly_partner<STEP>((uint32_t)v);
 }
 __device__ inline uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// uni() where ON, the plain (to the compiler: divergent) value elsewhere
+template <bool ON> __device__ inline uint32_t uni_if(uint32_t v) { return ON ? uni(v) : v; }
 __device__ inline uint32_t dpp_wave_sum_u32(uint32_t v) {  // total, wave-uniform (SGPR)
     v += bfly_partner<1>(v);
     v += bfly_partner<2>(v);
@@ -3403,8 +3405,9 @@ __device__ __forceinline__ uint32_t crc16_cols(const uint32_t *fbuf, const FbMap
 // ST: units of a two-channel stream's mid/side pass (chn 0..3 = left, right, mid, side; WIDE for the side signal).
 template <int DT, bool SUB = false, bool ST = false, bool WIDE = false>
 __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *raster, const EncodeParams &P,
-                                                const TileGeom *tiles, const TileNorm *norms,
-                                                const SubAnalysis *ana, uint8_t *arena, int64_t arena_cap,
+                                                const TileGeom *__restrict__ tiles,
+                                                const TileNorm *__restrict__ norms,
+                                                const SubAnalysis *__restrict__ ana, uint8_t *arena, int64_t arena_cap,
                                                 int64_t *frame_off, uint64_t *status, int *err, EncV3Shared &S,
                                                 int want, int64_t f, int lane, const int32_t *ftile,
                                                 PendingFrame &prev, const uint4 *hdr_tab, int hdr_n,
@@ -3413,8 +3416,9 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
                                                 int32_t *sub_est = nullptr) {
     using T = typename Elem<DT>::T;
     using Lane = std::conditional_t<WIDE, LaneWide, LanePairs>;
-    uint32_t *fbuf = S.bits[threadIdx.x >> 6];  // holds the pending frame `prev` (or zero) on entry
-    const int t = ftile[f];
+    // (uni: a 1-D launch of 256 threads, so a wave's 64 threads share threadIdx.x >> 6)
+    uint32_t *fbuf = S.bits[uni_if<!WIDE>(threadIdx.x >> 6)];  // holds the pending frame `prev` (or zero) on entry
+    const int t = ftile[f];  // (f is wave-uniform, see k_encode_v4: the frame's tables are scalar loads)
     const TileGeom g = tiles[t];
     const bool l0 = lane == 0;
     if (!SUB && g.partial && f - g.frame_base == g.nframes - 1) {
@@ -3527,16 +3531,24 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
     else if (Tt[2] <= min(Tt[3], Tt[4])) guess = 2;
     else if (Tt[3] <= Tt[4]) guess = 3;
     else guess = 4;
-    const uint32_t tg = guess == 0 ? Tt[0] : guess == 1 ? Tt[1] : guess == 2 ? Tt[2] : guess == 3 ? Tt[3] : Tt[4];
-    const double dn = (double)(n - 4);
-    const float fb1 = (float)(Tt[1] > 0 ? log(M_LN2 * (double)Tt[1] / dn) / M_LN2 : 0.0);
-    const float fbg = (float)(tg > 0 ? log(M_LN2 * (double)tg / dn) / M_LN2 : 0.0);
+    // libFLAC's float estimates fb(T) = (float)(T > 0 ? log(M_LN2 * T / (n - 4)) / M_LN2 : 0.0) of the order-1 total
+    // and of the guess's total tg gate the CONSTANT test (fb(Tt[1]) == 0.0f) and the fixed candidate
+    // (fb(tg) < sbps), tg = Tt[guess].  With n = 4096 neither needs the logs (tests/test_fixed_bits_bound.py evaluates
+    // both claims on the expression):
+    //  * fb(T) == 0.0f for T > 0 would need fl(fl(M_LN2 * T) / 4092) == 1.0, i.e. M_LN2 * T within an ulp of 4092:
+    //    T = 5903 gives 4091.65, T = 5904 gives 4092.34, no integer qualifies; for every other T, |log2| >= 1e-4,
+    //    far from a float zero.  So the test is exactly Tt[1] == 0.
+    //  * tg is the minimum of the five totals, so tg <= Tt[0], the sum of 4092 magnitudes of samples that fit sbps
+    //    signed bits (premise: every sample form coded here does -- normalised int16 >> w, mid ((L + R) >> 1) >> w,
+    //    the side signal at 17 bits, the generic normaliser's 16-bit output): tg <= 4092 * 2^(sbps - 1), so
+    //    fb(tg) <= sbps - 1 + log2(ln 2) < sbps - 1.5 and fb(tg) >= sbps never holds.
+    static_assert(n == 4096, "the fixed-estimate bounds above are argued for 4092 summed terms");
     bool constant = false;
-    if (fb1 == 0.0f) {
+    if (Tt[1] == 0) {
         Ls.fence();
         constant = dpp_wave_or_u32(Ls.diff_from_first()) == 0;
     }
-    const bool cand_fixed = !constant && !(fbg >= (float)sbps);
+    const bool cand_fixed = !constant;
     const bool cand_lpc = !constant && (A.flags & kFlagLpcOk);
     const int of = guess, ol = A.lpc_order, lshift = A.lpc_shift;
     // the fixed candidate's lane sum of |e_of(i)|, lane 0 from i = of (the totals start at 4: lane 0 adds its i < 4)
@@ -3888,18 +3900,30 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
 // SUB: the units are subframes -- (frame, channel) of a >= 3-channel stream, or of a two-channel stream's mid/side
 // pass (ST): left, right, mid in one launch, the 17-bit side signals (WIDE) in another.
 template <int DT, bool SUB = false, bool ST = false, bool WIDE = false>
-// (3 waves per SIMD for mono / >= 3-channel 16-bit units; 2 for the two-channel launches: L/R/M need 195 VGPRs, the
-// int32 side 256 -- capped from 262, a 32-byte spill: convert_2band encode 3.17 -> 2.78 ms against 1 wave per SIMD)
+// (3 waves per SIMD for mono / >= 3-channel 16-bit units; 2 for the two-channel launches: convert_2band encode
+// 3.17 -> 2.78 ms against 1 wave per SIMD.  With the frame state scalar the mono instance takes 140 VGPRs of its 168
+// and L/R/M 157; the int32 side, in its vector form, 255 without a spill)
 __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ? 2 : 3) : 1) k_encode_v4(const typename Elem<DT>::T *raster, EncodeParams P,
-                                                  const TileGeom *tiles, const TileNorm *norms, const int16_t *luts,
-                                                  const SubAnalysis *ana, uint8_t *arena, int64_t arena_cap,
+                                                  const TileGeom *__restrict__ tiles,
+                                                  const TileNorm *__restrict__ norms, const int16_t *__restrict__ luts,
+                                                  const SubAnalysis *__restrict__ ana, uint8_t *arena, int64_t arena_cap,
                                                   int64_t *frame_off, uint64_t *status, int *ticket_ctr, int *err,
                                                   const int32_t *__restrict__ ftile, const uint4 *__restrict__ hdr_tab,
                                                   int hdr_n, const uint32_t *__restrict__ pslots,
                                                   const int64_t *__restrict__ pbytes, uint32_t *sub_slots = nullptr,
                                                   int32_t *sub_bits = nullptr, int32_t *sub_est = nullptr) {
     __shared__ __attribute__((aligned(16))) EncV3Shared S;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // The tables this kernel only reads (tiles, norms, luts, ana, ftile, hdr_tab, pslots, pbytes) are written by
+    // earlier kernels of the stream, never by this one: const __restrict__, so loads at wave-uniform addresses are
+    // scalar loads.  The frame index is made provably wave-uniform below, which keeps everything decoded from it --
+    // tile geometry, normaliser, analysis, header row, field positions, look-back bounds -- in SGPRs and the
+    // branches on it scalar.
+    // The side-signal instance (WIDE) keeps its vector form: at its 256-VGPR cap the scalar control flow made the
+    // register allocator spill 43 of a lane's samples across load_lane's normalisation switch (244 bytes of scratch
+    // against 32).
+    constexpr bool kUni = !WIDE;
+    // (uni: the launch is 1-D with 256 threads, so the 64 threads of a wave share threadIdx.x >> 6)
+    const int wave = (int)uni_if<kUni>(threadIdx.x >> 6), lane = threadIdx.x & 63;
     for (int i = threadIdx.x; i < 4096; i += blockDim.x) (&S.crc8x[0][0])[i] = (&c_crc16x8[0][0])[i];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) S.crc8[i] = c_crc8[i];
     for (int i = threadIdx.x; i < 64; i += blockDim.x) S.xlo[i] = g_xpow_bytes[i];
@@ -3926,10 +3950,13 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
             S.want[sl] = (u0 < nunits) ? ftile[SUB ? u0 / upf : u0] : -1;
         }
         __syncthreads();
-        const int64_t fbase = (int64_t)S.ticket[sl] * 4;
+        // (uni: sl is the same in every thread, and thread 0 wrote both slots before the barrier: every lane reads
+        // the same LDS words)
+        const int64_t fbase = (int64_t)(int)uni_if<kUni>((uint32_t)S.ticket[sl]) * 4;
         if (fbase >= nunits) break;
-        const int want = S.want[sl];
-        if (want != S.lut_tile) {  // WG-uniform
+        const int want = (int)uni_if<kUni>((uint32_t)S.want[sl]);
+        // (uni: S.lut_tile is written by thread 0 only, with a barrier between that write and this read)
+        if (want != (int)uni_if<kUni>((uint32_t)S.lut_tile)) {  // WG-uniform
             const TileNorm tw = norms[want];
             if (tw.mode == kNormLut) {
                 const int64_t R = min(tw.imax - tw.imin, (int64_t)kLutCap - 1);
