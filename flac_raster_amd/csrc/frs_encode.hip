@@ -1,18 +1,29 @@
-// frs_encode.hip -- gfx950 encode path: raster tiles -> libFLAC-1.4.3-level-5-identical FLAC frames.
+// frs_encode.hip -- gfx950 encode path: raster tiles -> libFLAC-1.4.3-identical FLAC frames (level 5 by default).
 //
 // Reference path replaced (Youssef-Harby/flac-raster): cli.py:690-763 (create_streaming tile loop, band 1),
 // converter.py:56-86 (normalise to int16), converter.py:185-216 (interleave + pyflac StreamEncoder ->
 // libFLAC FLAC__stream_encoder_process_interleaved/finish at level 5, blocksize 4096).
 //
-// Kernels (one encode job = a set of tiles; every tile is one FLAC stream):
-//   k_stats_init / k_tile_stats / k_tile_finalize   per-tile min/max (np.min/np.max) + normalisation params
-//   k_analyze        lane = (frame, channel) subframe: wasted bits, fixed-predictor totals and the
-//                    tukey(0.5)-windowed autocorrelation (fp64, libFLAC's per-lag sequential order),
-//                    Levinson-Durbin, order guess, qlp quantisation        [fp64-VALU bound]
-//   k_encode_frames  workgroup = frame: candidate residuals, partition sums, Rice parameters, choice,
-//                    exact bit positions (block prefix scan) and LDS bit packing into a frame slot
-//   k_scan_sizes     exclusive scan of frame sizes -> arena offsets (tiles are consecutive frame runs)
-//   k_compact        workgroup = frame: CRC-16 (parallel GF(2) combine) + copy slot -> arena offset
+// One encode job = a set of tiles; every tile is one FLAC stream.  The device code comes first, by stage (tile
+// statistics, generic analysis, k_encode_frames, CRC-16 / scan / compact, the fast paths' loads and LUT, k_analyze_v3,
+// wave primitives, k_encode_v4, multi-channel assembly); the host code at the end plans a job (plan_encode), runs the
+// tile statistics (run_stats) and then one of three pipelines (EncodePath):
+//
+//   generic      any dtype, level, blocksize, bit depth
+//                k_analyze (+ k_analyze_fixed_wide, k_analyze_lpc_hi; k_zero_subframes for raw-frames tiles)
+//                -> k_encode_frames (+ k_zero_frames_emit) into slots -> k_scan_sizes -> k_compact (CRC-16) -> arena
+//   fast mono    16-bit mono streams of 4096-sample blocks at level 5 (the benchmark's C3 / C4 configs)
+//                [k_build_lut] -> k_analyze_v3 (tile statistics fused for small tiles)
+//                -> k_encode_v4: codes a frame per wave and stores it at the offset a decoupled look-back
+//                resolves, CRC-16 included
+//                -> k_fast_finish: tile offsets, min/max and flags in one packed copy
+//   fast multi / stereo   the same streams with 3..8 / 2 channels
+//                k_analyze_v3 -> k_encode_v4<SUB> (subframes into slots; stereo: L, R, M and the 17-bit S)
+//                -> k_mc_frame_bytes (sizes, stereo assignment) -> k_scan_sizes -> k_mc_assemble -> arena
+//   A tile's partial last frame on the fast paths: k_analyze_partial -> k_encode_frames -> k_seal_partial, copied in
+//   stream order by k_encode_v4 / k_mc_assemble.
+//
+// Every frame header is written by frame_header (frs_frame_header.h), on the device and for the host's header table.
 
 #include <type_traits>
 
@@ -20,6 +31,7 @@
 #include <unistd.h>
 
 #include "frs_internal.h"
+#include "frs_frame_header.h"
 
 namespace frs {
 
@@ -1155,65 +1167,7 @@ template <typename XT> struct EncShared {
 // Frame header of a generic-path frame (RFC 9639 9.1; libFLAC FLAC__frame_add_header) into h: fixed blocksize,
 // frame number fk (UTF-8), sample rate and bps codes, channel assignment code cac, CRC-8; returns its bytes
 __device__ inline int generic_frame_header(uint8_t *h, int n, const EncodeParams &P, int cac, uint32_t fk) {
-    int hb = 0;
-    int bsc, bsx = 0;
-    switch (n) {
-    case 192: bsc = 1; break;
-    case 576: bsc = 2; break;
-    case 1152: bsc = 3; break;
-    case 2304: bsc = 4; break;
-    case 4608: bsc = 5; break;
-    case 256: bsc = 8; break;
-    case 512: bsc = 9; break;
-    case 1024: bsc = 10; break;
-    case 2048: bsc = 11; break;
-    case 4096: bsc = 12; break;
-    case 8192: bsc = 13; break;
-    case 16384: bsc = 14; break;
-    case 32768: bsc = 15; break;
-    default: bsc = bsx = (n <= 256 ? 6 : 7); break;
-    }
-    int src, srx = 0;
-    const int sr = P.sample_rate;
-    switch (sr) {
-    case 88200: src = 1; break;
-    case 176400: src = 2; break;
-    case 192000: src = 3; break;
-    case 8000: src = 4; break;
-    case 16000: src = 5; break;
-    case 22050: src = 6; break;
-    case 24000: src = 7; break;
-    case 32000: src = 8; break;
-    case 44100: src = 9; break;
-    case 48000: src = 10; break;
-    case 96000: src = 11; break;
-    default:
-        if (sr <= 255000 && sr % 1000 == 0) src = srx = 12;
-        else if (sr % 10 == 0 && sr / 10 <= 65535) src = srx = 14;
-        else src = srx = 13;
-    }
-    int bpc = P.bps == 8 ? 1 : P.bps == 12 ? 2 : P.bps == 16 ? 4 : P.bps == 20 ? 5 : P.bps == 24 ? 6 : P.bps == 32 ? 7 : 0;
-    // channel assignment: nch - 1 (independent), 8 left-side, 9 right-side, 10 mid-side
-    h[hb++] = 0xFF;
-    h[hb++] = 0xF8;
-    h[hb++] = (uint8_t)((bsc << 4) | src);
-    h[hb++] = (uint8_t)((cac << 4) | (bpc << 1));
-    const uint32_t v = fk;
-    if (v < 0x80) h[hb++] = (uint8_t)v;
-    else if (v < 0x800) { h[hb++] = (uint8_t)(0xC0 | (v >> 6)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else if (v < 0x10000) { h[hb++] = (uint8_t)(0xE0 | (v >> 12)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else if (v < 0x200000) { h[hb++] = (uint8_t)(0xF0 | (v >> 18)); h[hb++] = (uint8_t)(0x80 | ((v >> 12) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else if (v < 0x4000000) { h[hb++] = (uint8_t)(0xF8 | (v >> 24)); h[hb++] = (uint8_t)(0x80 | ((v >> 18) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 12) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else { h[hb++] = (uint8_t)(0xFC | (v >> 30)); h[hb++] = (uint8_t)(0x80 | ((v >> 24) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 18) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 12) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    if (bsx == 6) h[hb++] = (uint8_t)(n - 1);
-    else if (bsx == 7) { h[hb++] = (uint8_t)((n - 1) >> 8); h[hb++] = (uint8_t)(n - 1); }
-    if (srx == 12) h[hb++] = (uint8_t)(sr / 1000);
-    else if (srx == 13) { h[hb++] = (uint8_t)(sr >> 8); h[hb++] = (uint8_t)sr; }
-    else if (srx == 14) { h[hb++] = (uint8_t)((sr / 10) >> 8); h[hb++] = (uint8_t)(sr / 10); }
-    uint8_t c = 0;
-    for (int i = 0; i < hb; i++) c = c_crc8[c ^ h[i]];
-    h[hb++] = c;
-    return hb;
+    return frame_header(h, n, P.sample_rate, P.bps, cac, fk, c_crc8);
 }
 
 // workgroup = frame.  ST: a two-channel stream -- the four signals L, R, M, S are evaluated (process_subframe_ each),
@@ -1781,17 +1735,6 @@ __global__ void k_gather_tile_off(const int64_t *frame_off, const TileGeom *tile
     if (t == ntiles) tile_off[t] = total;
 }
 
-// =================================================================================================
-// FAST PATH (16-bit mono streams: create-streaming band-1 tiles, converter bps 16)
-//   k_build_lut     per tile: pcm = lut[x - min] for x - min in [0, R] (exact double path, once per value)
-//   k_analyze_v3    lane = frame; 64-sample chunks loaded as 8 x 16 B per lane (no L1 reuse needed),
-//                   LUT normalisation, wave-uniform window from LDS, 9 fp64 FMA chains per lane
-//   k_encode_v3     persistent WGs, wave = frame, 64 consecutive samples per lane held as packed int16
-//                   pairs: fixed totals, v_dot2 residuals, partition sums by lane shuffles, Rice search,
-//                   exact bit positions by one wave scan, size published before LDS bit packing,
-//                   slice-by-4 CRC-16, decoupled look-back for the arena offset, 16-B aligned stores
-// =================================================================================================
-
 // exact converter.py normalisation of one element for the fast kernels (mode per tile)
 template <int DT>
 __device__ inline int32_t norm_fast(typename Elem<DT>::T x, const TileNorm &tn, const int16_t *lut) {
@@ -1897,10 +1840,6 @@ template <int DT, int N> struct ChunkN {
     static constexpr int kWords = (int)(N * sizeof(T) / 4);
     static_assert(kWords % 4 == 0, "chunk = whole 16-byte loads");
     uint32_t w[kWords];
-    __device__ inline void unpack(T *out) const {
-#pragma unroll
-        for (int j = 0; j < N; j++) out[j] = get(j);
-    }
     __device__ inline T get(int j) const {  // j must be a compile-time constant after unrolling
         if constexpr (sizeof(T) == 1) return (T)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
         else if constexpr (sizeof(T) == 2) return (T)((w[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
@@ -2131,39 +2070,6 @@ __global__ void __launch_bounds__(256) k_zero_frames_emit(EncodeParams P, const 
     if (lane == 0) frame_bytes[f] = (int64_t)((bits + 7) >> 3) + 2;
 }
 
-// normalise elements [8b, 8b + 8) of a chunk (b compile-time after unrolling)
-template <int DT>
-__device__ inline void norm_block8(const Chunk64<DT> &ch, int b, const TileNorm &tn, const int16_t *lut, int32_t *x) {
-    switch (tn.mode) {
-    case kNormLut: {
-        const int32_t mn = (int32_t)tn.imin;
-#pragma unroll
-        for (int j = 0; j < 8; j++) x[j] = (int32_t)lut[(int32_t)ch.get(8 * b + j) - mn];
-        break;
-    }
-    case kNormZero:
-#pragma unroll
-        for (int j = 0; j < 8; j++) x[j] = 0;
-        break;
-    case kNormFastDiv: {
-        const int32_t mn = (int32_t)tn.imin;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const double a = (double)(2 * ((int32_t)ch.get(8 * b + j) - mn));
-            const double q0 = a * tn.rinv;
-            const double r = fma(-q0, tn.den, a);
-            const double q1 = fma(r, tn.rinv, q0);
-            x[j] = (int32_t)(int16_t)(int32_t)((q1 - 1.0) * 32767.0);
-        }
-        break;
-    }
-    default:
-#pragma unroll
-        for (int j = 0; j < 8; j++) x[j] = norm_fast<DT>(ch.get(8 * b + j), tn, lut);
-        break;
-    }
-}
-
 // wasted bits, LPC order choice (expected bits), Levinson coefficients and quantisation of one frame from its
 // windowed autocorrelation sums (stream_encoder.c process_subframe_ / lpc.c)
 __device__ inline SubAnalysis analysis_finish(const double *acc, uint32_t or_acc, int n, const EncodeParams &P,
@@ -2309,12 +2215,6 @@ __device__ inline int32_t ana_norm(typename Elem<DT>::T x, const TileNorm &tn, c
     } else {
         return norm_fast<DT>(x, tn, glut);
     }
-}
-
-__device__ inline uint32_t ana_sad(uint32_t a, uint32_t b, uint32_t c) {  // |a - b| + c (v_sad_u32)
-    uint32_t d;
-    asm("v_sad_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
 }
 
 // ST: `base` is the left band and sig (0..3) the coded signal of a two-channel stream's mid/side pass: left, right,
@@ -2548,33 +2448,6 @@ __global__ void __launch_bounds__(256) k_analyze_v3(const typename Elem<DT>::T *
 #undef FRS_ANA_SIG
 }
 
-// ---- wave helpers (64 lanes)
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ inline uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ inline uint32_t wave_or_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-// exclusive scan of a 64-bit per-lane value
-__device__ inline uint64_t wave_excl_scan_u64(uint64_t v, int lane) {
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
-    return incl - v;
-}
-
 // ---- cross-lane primitives without LDS round trips: DPP within rows of 16, permlane16/32_swap across
 //      rows (gfx950).  Butterfly steps must be applied in order 1, 2, 4, 8, 16, 32 (the mirror patterns
 //      pair whole sub-groups only once the lower steps have made each sub-group uniform).
@@ -2686,34 +2559,11 @@ __device__ inline int32_t dot2(uint32_t a, uint32_t b, int32_t c) {
 }
 __device__ inline uint32_t pack2(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
 
-// residual of local sample index j (0..63) of this lane given even pairs E[] (E[m] = x[2m], x[2m+1]) and
-// odd pairs O[] (O[m] = x[2m-1], x[2m]), each array holding 4 history pairs from the previous lane
-// first (indices 0..3) then this lane's 32 pairs (4..35).  C[] = coefficient pairs (q1,q0),(q3,q2),...
-// residual of local sample index j (0..63, compile-time) of this lane given the even pairs E[] (E[0..3]:
-// the previous lane's last 8 samples, E[4 + m] = (x[2m], x[2m+1])).  C[] = (q1,q0),(q3,q2),(q5,q4),(q7,q6).
-// Odd j uses odd-aligned pairs (x[j-2], x[j-1]) = perm(E[m], E[m-1]).
 // first product of a residual chain as VOP3P with an inline-zero accumulator (v_dot2c would need a v_mov 0)
 __device__ inline int32_t dot2_z(uint32_t a, uint32_t b) {
     int32_t d;
     asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(a), "v"(b));
     return d;
-}
-
-__device__ inline int32_t residual_at(const uint32_t *E, const uint32_t *C, int shift, int j, int32_t x) {
-    int32_t s = 0;
-    const int m = 4 + (j >> 1);
-    if ((j & 1) == 0) {
-        s = dot2_z(E[m - 1], C[0]);
-        s = dot2(E[m - 2], C[1], s);
-        s = dot2(E[m - 3], C[2], s);
-        s = dot2(E[m - 4], C[3], s);
-    } else {
-        s = dot2_z(__builtin_amdgcn_perm(E[m], E[m - 1], 0x05040302u), C[0]);
-        s = dot2(__builtin_amdgcn_perm(E[m - 1], E[m - 2], 0x05040302u), C[1], s);
-        s = dot2(__builtin_amdgcn_perm(E[m - 2], E[m - 3], 0x05040302u), C[2], s);
-        s = dot2(__builtin_amdgcn_perm(E[m - 3], E[m - 4], 0x05040302u), C[3], s);
-    }
-    return x - (s >> shift);
 }
 
 // residuals of samples 2m and 2m+1 of this lane with their v_dot2 chains interleaved (no dependent-dot
@@ -2735,15 +2585,6 @@ __device__ inline void residual_pair(const uint32_t *E, const uint32_t *C, int s
     const uint32_t v = E[b];
     re = (int32_t)(int16_t)(v & 0xFFFFu) - (se >> shift);
     ro = ((int32_t)v >> 16) - (so >> shift);
-}
-
-__device__ inline void lds_put_bits(uint32_t *buf, uint32_t pos, uint32_t val, int nbits) {
-    const uint32_t wi = pos >> 5;
-    const int off = (int)(pos & 31);
-    const uint64_t v = (uint64_t)val << (64 - off - nbits);
-    atomicOr(&buf[wi], (uint32_t)(v >> 32));
-    const uint32_t lo = (uint32_t)v;
-    if (lo) atomicOr(&buf[wi + 1], lo);
 }
 
 constexpr uint64_t kFlagAgg = 1ull << 62, kFlagIncl = 2ull << 62, kValMask = (1ull << 62) - 1;
@@ -2864,33 +2705,6 @@ struct PendingFrame {  // a frame whose bytes sit in the wave's bit buffer, offs
     bool ok = true;
     FbMap map{1, 1u << 20, 63};  // the frame's buffer layout
 };
-
-__device__ inline void sample_rate_code(int sr, int &src, int &srx) {  // RFC 9639 9.1.2
-    srx = 0;
-    switch (sr) {
-    case 88200: src = 1; break;
-    case 176400: src = 2; break;
-    case 192000: src = 3; break;
-    case 8000: src = 4; break;
-    case 16000: src = 5; break;
-    case 22050: src = 6; break;
-    case 24000: src = 7; break;
-    case 32000: src = 8; break;
-    case 44100: src = 9; break;
-    case 48000: src = 10; break;
-    case 96000: src = 11; break;
-    default:
-        if (sr <= 255000 && sr % 1000 == 0) src = srx = 12;
-        else if (sr % 10 == 0 && sr / 10 <= 65535) src = srx = 14;
-        else src = srx = 13;
-    }
-}
-
-// bytes of a fixed-blocksize (4096) frame header incl. CRC-8: sync/codes (4) + UTF-8 frame number + rate ext
-__device__ inline uint32_t frame_header_bytes(uint32_t v, int srx) {
-    const uint32_t u = v < 0x80 ? 1 : v < 0x800 ? 2 : v < 0x10000 ? 3 : v < 0x200000 ? 4 : v < 0x4000000 ? 5 : 6;
-    return 4 + u + (srx == 12 ? 1 : (srx == 13 || srx == 14) ? 2 : 0) + 1;
-}
 
 // Offset of a finished frame (decoupled look-back), inclusive publish, store of its bytes from the wave's
 // bit buffer, and re-zeroing of that buffer.
@@ -3997,26 +3811,7 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
 // frame header of a full 4096-sample frame (RFC 9639 9.1, as k_encode_frames writes it); returns its bytes
 // chcode: the channel assignment nibble (nch - 1 for independent channels; 8 / 9 / 10 left-side / right-side / mid-side)
 __device__ inline int mc_frame_header(uint8_t *h, uint32_t v, int chcode, int sr) {
-    int src, srx;
-    sample_rate_code(sr, src, srx);
-    int hb = 0;
-    h[hb++] = 0xFF;
-    h[hb++] = 0xF8;
-    h[hb++] = (uint8_t)((12 << 4) | src);
-    h[hb++] = (uint8_t)((chcode << 4) | (4 << 1));
-    if (v < 0x80) h[hb++] = (uint8_t)v;
-    else if (v < 0x800) { h[hb++] = (uint8_t)(0xC0 | (v >> 6)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else if (v < 0x10000) { h[hb++] = (uint8_t)(0xE0 | (v >> 12)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else if (v < 0x200000) { h[hb++] = (uint8_t)(0xF0 | (v >> 18)); h[hb++] = (uint8_t)(0x80 | ((v >> 12) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else if (v < 0x4000000) { h[hb++] = (uint8_t)(0xF8 | (v >> 24)); h[hb++] = (uint8_t)(0x80 | ((v >> 18) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 12) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    else { h[hb++] = (uint8_t)(0xFC | (v >> 30)); h[hb++] = (uint8_t)(0x80 | ((v >> 24) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 18) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 12) & 0x3F)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-    if (srx == 12) h[hb++] = (uint8_t)(sr / 1000);
-    else if (srx == 13) { h[hb++] = (uint8_t)(sr >> 8); h[hb++] = (uint8_t)sr; }
-    else if (srx == 14) { h[hb++] = (uint8_t)((sr / 10) >> 8); h[hb++] = (uint8_t)(sr / 10); }
-    uint8_t c = 0;
-    for (int i = 0; i < hb; i++) c = c_crc8[c ^ h[i]];
-    h[hb++] = c;
-    return hb;
+    return frame_header(h, 4096, sr, 16, chcode, v, c_crc8);
 }
 
 // A two-channel stream's frame (P.nvch == 4: L, R, M, S coded): libFLAC process_subframes_ keeps the assignment with
@@ -4204,14 +3999,19 @@ __global__ void k_fast_finish(const int64_t *frame_off, const uint64_t *status, 
 // ------------------------------------------------------------------------------------- host side
 static bool g_tables_ready[64];
 
+// the CRC-8 table of the frame headers: built once, uploaded as c_crc8 and used by the host's own header table
+static const uint8_t *host_crc8() {
+    static uint8_t t[256];
+    static const bool ready = (crc8_table(t), true);
+    (void)ready;
+    return t;
+}
+
 static int upload_tables(frs_ctx *ctx) {
     if (g_tables_ready[ctx->device]) return FRS_OK;
-    uint8_t t8[256];
+    const uint8_t *t8 = host_crc8();
     uint16_t t16[256];
     for (int i = 0; i < 256; i++) {
-        uint8_t c = (uint8_t)i;
-        for (int k = 0; k < 8; k++) c = (c & 0x80) ? (uint8_t)((c << 1) ^ 0x07) : (uint8_t)(c << 1);
-        t8[i] = c;
         uint16_t d = (uint16_t)(i << 8);
         for (int k = 0; k < 8; k++) d = (d & 0x8000) ? (uint16_t)((d << 1) ^ 0x8005) : (uint16_t)(d << 1);
         t16[i] = d;
@@ -4232,7 +4032,7 @@ static int upload_tables(frs_ctx *ctx) {
         xp[j] = (uint16_t)v;
         v = mulmod(v, v);
     }
-    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_crc8), t8, sizeof(t8), 0, hipMemcpyHostToDevice, ctx->stream));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_crc8), t8, 256, 0, hipMemcpyHostToDevice, ctx->stream));
     FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_crc16), t16, sizeof(t16), 0, hipMemcpyHostToDevice, ctx->stream));
     FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_xpow8), xp, sizeof(xp), 0, hipMemcpyHostToDevice, ctx->stream));
     // slice-by-16 tables: T_k[v] = T_{k-1}[v] advanced by one zero byte
@@ -4337,30 +4137,124 @@ int64_t arena_bound(const frs_encode_desc *d) {
     return nframes * (slot_words_for(d) * 4) + 64;
 }
 
-constexpr int kFastDeclined = 1000;  // run_encode: the fast path hit a frame it cannot hold; rerun generic
+constexpr int kFastDeclined = 1000;  // a fast path met a frame it cannot hold: run_encode_any reruns the generic path
 
-template <int DT>
-static int run_encode(frs_ctx *ctx, const frs_encode_desc *d, const void *raster_dev, void *arena_dev,
-                      int64_t arena_cap, int64_t *tile_off, double *tile_min, double *tile_max, bool allow_fast) {
+// FLAC__window_tukey(p) computed in double with the host libm cos, stored as float (window.c)
+static std::vector<float> tukey_window(int L, float p) {
+    std::vector<float> win(L, 1.0f);
+    const int Np = (int)(p / 2.0f * (float)L) - 1;
+    if (Np > 0)
+        for (int k = 0; k <= Np; k++) {
+            win[k] = (float)(0.5f - 0.5f * cos(M_PI * k / Np));
+            win[L - Np - 1 + k] = (float)(0.5f - 0.5f * cos(M_PI * (k + Np) / Np));
+        }
+    return win;
+}
+
+static int upload_window(frs_ctx *ctx, DevBuf &buf, int L, float p) {
+    const std::vector<float> win = tukey_window(L, p);
+    FRS_HIP(buf.ensure(sizeof(float) * L));
+    FRS_HIP(hipMemcpyAsync(buf.ptr, win.data(), sizeof(float) * L, hipMemcpyHostToDevice, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    return FRS_OK;
+}
+
+// The widest of `classes` (bytes, widest first) that divides the base address and every one of `strides` (bytes);
+// 0 when none does.  Each caller lists exactly the strides its kernel's vector loads step by.
+static int align_class(uintptr_t base, std::initializer_list<int> classes, std::initializer_list<int64_t> strides) {
+    for (int a : classes) {
+        bool ok = base % a == 0;
+        for (int64_t s : strides) ok = ok && s % a == 0;
+        if (ok) return a;
+    }
+    return 0;
+}
+
+// A persistent kernel of 256-thread work-groups taking 4 units each: as many work-groups as fit the device (one
+// occupancy query per instantiation, kept in nwg_max; the same gfx950 target for every device), at most units / 4.
+template <typename K, typename... Args>
+static int launch_resident(frs_ctx *ctx, K kern, int &nwg_max, int64_t units, Args... args) {
+    if (nwg_max == 0) FRS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nwg_max, kern, 256, 0));
+    int64_t grid = (int64_t)std::max(1, nwg_max) * ctx->num_cus;
+    grid = std::min<int64_t>(grid, (units + 3) / 4);
+    kern<<<(unsigned)grid, 256, 0, ctx->stream>>>(args...);
+    return FRS_OK;
+}
+
+// The pipelines of an encode job.  The fast ones hard-code level 5's search for 16-bit streams of 4096-sample blocks
+// from integer rasters.  A tile whose pixel count is not a multiple of 4096 ends in a partial frame: those frames (at
+// most one per tile) are coded by the generic kernels first and the fast encoders copy them in stream order.
+//   FastMono    one channel: k_analyze_v3 -> k_encode_v4 writes the arena itself (look-back offsets).
+//   FastMulti   3..8 channels (plain convert of a multi-band raster): libFLAC codes the channels independently, so
+//               k_encode_v4 codes subframes, k_mc_frame_bytes sizes the frames and k_mc_assemble joins them.
+//   FastStereo  two channels: libFLAC's mid/side pass codes L, R, M and S (17 bits) and keeps the cheapest pair by
+//               their estimates (k_mc_frame_bytes picks, k_mc_assemble joins).
+//   Generic     everything else: k_analyze* -> k_encode_frames into slots -> k_scan_sizes -> k_compact.
+enum class EncodePath { Generic, FastMono, FastMulti, FastStereo };
+
+static EncodePath choose_path(const frs_ctx *ctx, const frs_encode_desc *d, const EncodeParams &P, bool is_float,
+                              bool allow_fast) {
+    const bool eligible = allow_fast && !ctx->force_generic && d->compression_level == 5 && P.bps == 16 &&
+                          P.norm_mode == 0 && d->blocksize == 4096 && !is_float;
+    if (!eligible) return EncodePath::Generic;
+    if (P.nch == 1) return EncodePath::FastMono;
+    if (P.nch == 2) return P.nvch == 4 ? EncodePath::FastStereo : EncodePath::Generic;
+    return P.nch <= 8 ? EncodePath::FastMulti : EncodePath::Generic;
+}
+
+// What the steps of one encode call share: filled by plan_encode, read by the rest.
+template <int DT> struct EncodeJob {
     using T = typename Elem<DT>::T;
-    // job geometry cache (frs_ctx::geo_*): everything the tile table, partial marking and wave table depend on
-    const std::vector<int64_t> key = {d->height, d->width, d->tile_h, d->tile_w, d->tile_begin, d->tile_end,
-                                      d->blocksize, d->nbands, d->dtype, d->bits_per_sample, d->norm_mode,
-                                      (allow_fast && !ctx->force_generic) ? 1 : 0, d->compression_level};
-    const bool geo_hit = !ctx->geo_key.empty() && ctx->geo_key == key;
-    std::vector<TileGeom> tiles_local;
-    std::vector<TileGeom> &tiles = geo_hit ? ctx->geo_tiles : tiles_local;
-    int64_t nframes = ctx->geo_nframes;
-    if (!geo_hit) {
-        ctx->geo_key.clear();  // the device copies are rewritten below; valid again once uploaded
-        build_tiles(d, tiles, nframes);
-    }
-    const int ntiles = (int)tiles.size();
-    if (ntiles == 0) {
-        tile_off[0] = 0;
-        return FRS_OK;
-    }
+    frs_ctx *ctx;
+    const frs_encode_desc *d;
+    hipStream_t st;
     EncodeParams P;
+    LevelParams lv;
+    EncodePath path;
+    // geometry: the context's cache on a hit, else built here (and cached by the fast paths)
+    std::vector<int64_t> key;
+    bool geo_hit, dev_tiles;  // the cache holds this job; its device tile table is still in place
+    std::vector<TileGeom> tiles_local, *tiles;
+    int ntiles;
+    int64_t nframes, npartial;
+    int64_t *hplist;                    // pinned: partial-frame list
+    size_t pin_wt, pin_res, res_bytes;  // pinned staging: wave table, packed results
+    bool stats_vec, fuse_stats;
+    // device
+    const T *raster;
+    uint8_t *arena;
+    int64_t arena_cap;
+    TileGeom *dtiles;
+    TileNorm *dnorms;
+    SubAnalysis *dana;
+    int *err_flag;
+    // results
+    int64_t *tile_off;
+    double *tile_min, *tile_max;
+    bool stereo_fast() const { return path == EncodePath::FastStereo; }
+};
+
+// Tiles (or the geometry cache's), EncodeParams, the buffers every path needs, the path, the partial-frame list of the
+// fast paths, window and tile table on the device.  ntiles == 0: nothing else is set up.
+template <int DT>
+static int plan_encode(EncodeJob<DT> &J, const void *raster_dev, bool allow_fast) {
+    using T = typename Elem<DT>::T;
+    frs_ctx *ctx = J.ctx;
+    const frs_encode_desc *d = J.d;
+    // everything the tile table, partial marking and wave table depend on
+    J.key = {d->height, d->width, d->tile_h, d->tile_w, d->tile_begin, d->tile_end, d->blocksize, d->nbands, d->dtype,
+             d->bits_per_sample, d->norm_mode, (allow_fast && !ctx->force_generic) ? 1 : 0, d->compression_level};
+    J.geo_hit = !ctx->geo.key.empty() && ctx->geo.key == J.key;
+    J.tiles = J.geo_hit ? &ctx->geo.tiles : &J.tiles_local;
+    J.nframes = ctx->geo.nframes;
+    if (!J.geo_hit) {
+        ctx->geo.key.clear();  // the device copies are rewritten below; valid again once uploaded
+        build_tiles(d, *J.tiles, J.nframes);
+    }
+    const int ntiles = J.ntiles = (int)J.tiles->size();
+    if (ntiles == 0) return FRS_OK;
+    const int64_t nframes = J.nframes;
+    EncodeParams &P = J.P;
     P.row_stride = d->row_stride;
     P.band_stride = d->band_stride;
     P.band0 = d->band0;
@@ -4375,7 +4269,7 @@ static int run_encode(frs_ctx *ctx, const frs_encode_desc *d, const void *raster
     P.ntiles = ntiles;
     P.norm_mode = d->norm_mode;
     P.vec_ok = 0;
-    const LevelParams lv = level_params(d->compression_level);
+    const LevelParams lv = J.lv = level_params(d->compression_level);
     // two channels with mid/side (levels 2, 5): L, R, mid, side (exhaustive mid/side stereo)
     P.nvch = (P.nch == 2 && lv.mid_side) ? 4 : P.nch;
     P.max_lpc = lv.max_lpc;
@@ -4387,492 +4281,451 @@ static int run_encode(frs_ctx *ctx, const frs_encode_desc *d, const void *raster
         P.loose_frames = (int32_t)(uint32_t)((double)d->sample_rate * 0.4 / (double)d->blocksize + 0.5);
         if (P.loose_frames == 0) P.loose_frames = 1;
     }
-    const bool level5 = d->compression_level == 5;  // the fast kernels hard-code level 5's search
+    J.path = choose_path(ctx, d, P, Elem<DT>::is_float, allow_fast);
 
-    int rc = upload_tables(ctx);
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
+    if (const int rc = upload_tables(ctx)) return rc;
+    hipStream_t st = J.st = ctx->stream;
     FRS_HIP(ctx->tiles.ensure(sizeof(TileGeom) * ntiles));
     FRS_HIP(ctx->norms.ensure(sizeof(TileNorm) * ntiles));
     FRS_HIP(ctx->analysis.ensure(sizeof(SubAnalysis) * nframes * P.nvch));
     FRS_HIP(ctx->frame_bytes.ensure(sizeof(int64_t) * (nframes + 1) + 64));
     FRS_HIP(ctx->frame_off.ensure(sizeof(int64_t) * (nframes + 1)));
     FRS_HIP(ctx->tile_sizes.ensure(sizeof(int64_t) * (ntiles + 1) + 64));
-    // pinned staging: tiles | wave table | packed results (the previous call has synchronised, so it is free)
-    const size_t pin_tiles = 0, pin_wt = (sizeof(TileGeom) * ntiles + 255) & ~(size_t)255;
+    // pinned staging: tiles | wave table | packed results | partial-frame list (the previous call has synchronised,
+    // so it is free)
+    const size_t pin_tiles = 0;
+    J.pin_wt = (sizeof(TileGeom) * ntiles + 255) & ~(size_t)255;
     const size_t wt_cap = (size_t)(nframes / 64 + ntiles + 1) * (size_t)std::max(1, (int)P.nvch);
-    const size_t pin_res = (pin_wt + sizeof(int2) * wt_cap + 255) & ~(size_t)255;
-    const size_t res_bytes = sizeof(int64_t) * (3 * (size_t)ntiles + 2);
-    const size_t pin_pl = (pin_res + res_bytes + 255) & ~(size_t)255;  // partial-frame list of the fast path
+    J.pin_res = (J.pin_wt + sizeof(int2) * wt_cap + 255) & ~(size_t)255;
+    J.res_bytes = sizeof(int64_t) * (3 * (size_t)ntiles + 2);
+    const size_t pin_pl = (J.pin_res + J.res_bytes + 255) & ~(size_t)255;
     FRS_HIP(ctx->pin.ensure(pin_pl + sizeof(int64_t) * (size_t)ntiles));
-    // fast path: mono 16-bit streams of 4096-sample blocks.  A tile whose pixel count is not a multiple of 4096
-    // ends in a partial frame: those frames (at most one per tile) are coded by the generic kernels first and
-    // the fast encoder copies them into the arena in stream order
-    const bool fast = allow_fast && !ctx->force_generic && level5 && P.bps == 16 && P.nch == 1 && P.norm_mode == 0 &&
-                      d->blocksize == 4096 && !Elem<DT>::is_float;
-    // multi-channel streams of >= 3 channels (plain convert of a multi-band raster): libFLAC codes their channels
-    // independently, so the fast kernels code the subframes and k_mc_assemble joins them.  Two channels (st2):
-    // libFLAC's mid/side pass codes L, R, M and S (17 bits) as subframes and keeps the cheapest pair by their
-    // estimates (k_mc_frame_bytes picks, k_mc_assemble joins)
-    const bool st2 = allow_fast && !ctx->force_generic && level5 && P.bps == 16 && P.nch == 2 && P.nvch == 4 &&
-                     P.norm_mode == 0 && d->blocksize == 4096 && !Elem<DT>::is_float;
-    const bool mc = st2 || (allow_fast && !ctx->force_generic && level5 && P.bps == 16 && P.nch >= 3 && P.nch <= 8 &&
-                            P.norm_mode == 0 && d->blocksize == 4096 && !Elem<DT>::is_float);
-    int64_t npartial = 0;
-    int64_t *hplist = ctx->pin.at<int64_t>(pin_pl);
-    if (geo_hit) {
-        npartial = (int64_t)ctx->geo_plist.size();
-        if (npartial) memcpy(hplist, ctx->geo_plist.data(), sizeof(int64_t) * (size_t)npartial);
-    } else if (fast || mc) {
-        for (TileGeom &tg : tiles)
+    J.npartial = 0;
+    J.hplist = ctx->pin.at<int64_t>(pin_pl);
+    if (J.geo_hit) {
+        J.npartial = (int64_t)ctx->geo.plist.size();
+        if (J.npartial) memcpy(J.hplist, ctx->geo.plist.data(), sizeof(int64_t) * (size_t)J.npartial);
+    } else if (J.path != EncodePath::Generic) {
+        for (TileGeom &tg : *J.tiles)
             if (((int64_t)tg.h * tg.w) % d->blocksize != 0) {
-                hplist[npartial] = tg.frame_base + tg.nframes - 1;
-                tg.partial = (int32_t)(++npartial);
+                J.hplist[J.npartial] = tg.frame_base + tg.nframes - 1;
+                tg.partial = (int32_t)(++J.npartial);
             }
     }
     // device copies of the cached geometry still in place (a grown buffer is a new allocation)
-    const bool dev_tiles = geo_hit && ctx->geo_ptrs[0] == ctx->tiles.ptr;
+    J.dev_tiles = J.geo_hit && ctx->geo.dev_tiles == ctx->tiles.ptr;
     if (ctx->window_bs != d->blocksize) {
-        std::vector<float> win(d->blocksize, 1.0f);
-        // FLAC__window_tukey(0.5) computed in double with the host libm cos, stored as float (window.c)
-        const float p = 0.5f;
-        const int L = d->blocksize;
-        const int Np = (int)(p / 2.0f * (float)L) - 1;
-        if (Np > 0)
-            for (int k = 0; k <= Np; k++) {
-                win[k] = (float)(0.5f - 0.5f * cos(M_PI * k / Np));
-                win[L - Np - 1 + k] = (float)(0.5f - 0.5f * cos(M_PI * (k + Np) / Np));
-            }
-        FRS_HIP(ctx->window.ensure(sizeof(float) * L));
-        FRS_HIP(hipMemcpyAsync(ctx->window.ptr, win.data(), sizeof(float) * L, hipMemcpyHostToDevice, st));
-        FRS_HIP(hipStreamSynchronize(st));
+        if (const int rc = upload_window(ctx, ctx->window, d->blocksize, 0.5f)) return rc;
         ctx->window_bs = d->blocksize;
     }
-    if (!dev_tiles) {
-        memcpy(ctx->pin.at<TileGeom>(pin_tiles), tiles.data(), sizeof(TileGeom) * ntiles);
+    if (!J.dev_tiles) {
+        memcpy(ctx->pin.at<TileGeom>(pin_tiles), J.tiles->data(), sizeof(TileGeom) * ntiles);
         FRS_HIP(hipMemcpyAsync(ctx->tiles.ptr, ctx->pin.at<TileGeom>(pin_tiles), sizeof(TileGeom) * ntiles,
                                hipMemcpyHostToDevice, st));
     }
-    int *err_flag = reinterpret_cast<int *>(ctx->frame_bytes.as<int64_t>() + nframes + 1);
-    FRS_HIP(hipMemsetAsync(err_flag, 0, sizeof(int), st));
+    J.err_flag = reinterpret_cast<int *>(ctx->frame_bytes.as<int64_t>() + nframes + 1);
+    FRS_HIP(hipMemsetAsync(J.err_flag, 0, sizeof(int), st));
+    J.raster = reinterpret_cast<const T *>(raster_dev);
+    J.dtiles = ctx->tiles.as<TileGeom>();
+    J.dnorms = ctx->norms.as<TileNorm>();
+    J.dana = ctx->analysis.as<SubAnalysis>();
 
-    const T *raster = reinterpret_cast<const T *>(raster_dev);
-    TileGeom *dtiles = ctx->tiles.as<TileGeom>();
-    TileNorm *dnorms = ctx->norms.as<TileNorm>();
-    SubAnalysis *dana = ctx->analysis.as<SubAnalysis>();
-
-    hipEvent_t ev;
     bool one_wave_tiles = true;
-    for (const TileGeom &tg : tiles) one_wave_tiles = one_wave_tiles && tg.nframes <= 64;
-    bool stats_vec = false;
+    for (const TileGeom &tg : *J.tiles) one_wave_tiles = one_wave_tiles && tg.nframes <= 64;
+    J.stats_vec = false;
     if constexpr (sizeof(T) <= 2 && !Elem<DT>::is_float) {
         const int64_t es = (int64_t)sizeof(T);
         const uintptr_t b = reinterpret_cast<uintptr_t>(raster_dev) + (uintptr_t)(d->band0 * d->band_stride * es);
-        stats_vec = (b % 16 == 0) && ((d->row_stride * es) % 16 == 0) && ((d->band_stride * es) % 16 == 0) &&
-                    ((d->tile_w * es) % 16 == 0) && ((d->width * es) % 16 == 0);
+        J.stats_vec = align_class(b, {16}, {d->row_stride * es, d->band_stride * es, d->tile_w * es, d->width * es}) == 16;
     }
-    // Tile stats on the fast path (16-bit samples, 16-B aligned rows, one wave per tile): fused into the analysis
+    // Tile stats on the mono fast path (16-bit samples, 16-B aligned rows, one wave per tile): fused into the analysis
     // launch (k_analyze_v3<DT, false, true>: min/max, parameters and LUT per wave).  Otherwise the stats kernels
     // run before the analysis.
-    const bool fuse_stats = fast && stats_vec && sizeof(T) == 2 && one_wave_tiles;
-    // 1. tile stats
-    if (!fuse_stats) {
-        prof_begin(ctx, "stats", &ev);
-        k_stats_init<<<(ntiles + 255) / 256, 256, 0, st>>>(dnorms, ntiles);
-        if (stats_vec) {
-            const int64_t es = (int64_t)sizeof(T);
-            const int64_t px = (int64_t)d->tile_h * d->tile_w * d->nbands;
-            // ~256 KB per work-group, at least ~2048 work-groups overall
-            int splits = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)d->tile_h * d->nbands, px * es / (256 << 10)));
-            while ((int64_t)splits * ntiles < 2048 && splits < d->tile_h * d->nbands) splits++;
-            dim3 grid(splits, ntiles);
-            if constexpr (sizeof(T) <= 2 && !Elem<DT>::is_float)
-                k_tile_stats_vec<DT><<<grid, 256, 0, st>>>(raster, P, dtiles, dnorms, splits);
-        } else {
-            int64_t rows = (int64_t)d->tile_h * d->nbands;
-            int splits = (int)std::min<int64_t>(rows, std::max<int64_t>(1, (int64_t)4096 / ntiles));
-            if (splits < 1) splits = 1;
-            dim3 grid(splits, ntiles);
-            k_tile_stats<DT><<<grid, 256, 0, st>>>(raster, P, dtiles, dnorms, splits);
-        }
-        k_tile_finalize<DT><<<(ntiles + 255) / 256, 256, 0, st>>>(dnorms, ntiles, P.norm_mode, P.scale_bits);
-        prof_end(ctx, "stats", ev);
+    J.fuse_stats = J.path == EncodePath::FastMono && J.stats_vec && sizeof(T) == 2 && one_wave_tiles;
+    return FRS_OK;
+}
+
+// 1. tile stats: min/max per tile (np.min / np.max) and the normalisation parameters
+template <int DT>
+static void run_stats(EncodeJob<DT> &J) {
+    using T = typename Elem<DT>::T;
+    frs_ctx *ctx = J.ctx;
+    const frs_encode_desc *d = J.d;
+    const int ntiles = J.ntiles;
+    hipEvent_t ev;
+    prof_begin(ctx, "stats", &ev);
+    k_stats_init<<<(ntiles + 255) / 256, 256, 0, J.st>>>(J.dnorms, ntiles);
+    if (J.stats_vec) {
+        const int64_t es = (int64_t)sizeof(T);
+        const int64_t px = (int64_t)d->tile_h * d->tile_w * d->nbands;
+        // ~256 KB per work-group, at least ~2048 work-groups overall
+        int splits = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)d->tile_h * d->nbands, px * es / (256 << 10)));
+        while ((int64_t)splits * ntiles < 2048 && splits < d->tile_h * d->nbands) splits++;
+        dim3 grid(splits, ntiles);
+        if constexpr (sizeof(T) <= 2 && !Elem<DT>::is_float)
+            k_tile_stats_vec<DT><<<grid, 256, 0, J.st>>>(J.raster, J.P, J.dtiles, J.dnorms, splits);
+    } else {
+        int64_t rows = (int64_t)d->tile_h * d->nbands;
+        int splits = (int)std::min<int64_t>(rows, std::max<int64_t>(1, (int64_t)4096 / ntiles));
+        if (splits < 1) splits = 1;
+        dim3 grid(splits, ntiles);
+        k_tile_stats<DT><<<grid, 256, 0, J.st>>>(J.raster, J.P, J.dtiles, J.dnorms, splits);
     }
-    if constexpr (!Elem<DT>::is_float) if (fast || mc) {
-        const int es = (int)sizeof(T);
-        // alignment class of the 64-sample row segments (tiles whose width is a multiple of 64): the widest of 16,
-        // 8, 4 bytes dividing the band base, the row stride and the tile width in bytes
-        const uintptr_t b0 = reinterpret_cast<uintptr_t>(raster_dev) + (size_t)d->band0 * d->band_stride * es;
-        P.vec_ok = 0;
-        for (int a : {16, 8, 4})
-            if (P.vec_ok == 0 && (d->row_stride * es) % a == 0 && b0 % a == 0 && ((int64_t)d->tile_w * es) % a == 0)
-                P.vec_ok = a;
-        FRS_HIP(ctx->luts.ensure(sizeof(int16_t) * (size_t)kLutCap * ntiles));
-        FRS_HIP(ctx->status.ensure(sizeof(uint64_t) * (nframes + 1) + 64));
-        if (!fuse_stats) k_build_lut<DT><<<ntiles, 256, 0, st>>>(dnorms, ctx->luts.as<int16_t>());
-        FRS_HIP(ctx->frame_tile.ensure(sizeof(int32_t) * nframes));
-        if (!(dev_tiles && ctx->geo_ptrs[3] == ctx->frame_tile.ptr))
-            k_frame_tile<<<ntiles, 64, 0, st>>>(dtiles, ntiles, ctx->frame_tile.as<int32_t>());
-        {
-            // wave table: (tile, first frame) per wave, up to 64 frames of one tile each
-            int nwaves = ctx->geo_nwaves;
-            if (!(dev_tiles && ctx->geo_ptrs[1] == ctx->wave_tab.ptr)) {
-                int2 *wt = ctx->pin.at<int2>(pin_wt);
-                nwaves = 0;
-                for (int ti = 0; ti < ntiles; ti++)
-                    for (int c = 0; c < P.nvch; c++)  // (tile, first frame | coded signal << 24)
-                        for (int k0 = 0; k0 < tiles[ti].nframes; k0 += 64) wt[nwaves++] = make_int2(ti, k0 | (c << 24));
-                FRS_HIP(ctx->wave_tab.ensure(sizeof(int2) * nwaves));
-                FRS_HIP(hipMemcpyAsync(ctx->wave_tab.ptr, wt, sizeof(int2) * nwaves, hipMemcpyHostToDevice, st));
-            }
-            prof_begin(ctx, "analyze", &ev);
-            const unsigned wgrid = (unsigned)((nwaves + 3) / 4);
-            const int2 *wtab = ctx->wave_tab.as<int2>();
-            // small jobs with fused stats (C3): the prefetching form (FRS_ANA_PF=0/1 forces either).  Measured (round 6,
-            // one box): C3 analysis 0.348 -> 0.322 ms; the Sentinel-2 example's separate-stats launch 0.529 -> 0.620 ms
-            // and C4 1.30 -> 1.31-1.33 ms, so those keep the plain form
-            const char *pf_env = getenv("FRS_ANA_PF");
-            const bool pf = !st2 && (pf_env ? atoi(pf_env) == 1 : fuse_stats && nwaves <= kPfMaxWaves);
-            if (pf) {
-                if (fuse_stats) {
-                    if constexpr (sizeof(T) == 2)
-                        k_analyze_v3<DT, false, true, false, true><<<wgrid, 256, 0, st>>>(
-                            raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(), ctx->window.as<float>(), dana, wtab, nwaves);
-                } else {
-                    k_analyze_v3<DT, false, false, false, true><<<wgrid, 256, 0, st>>>(
-                        raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(), ctx->window.as<float>(), dana, wtab, nwaves);
-                }
-            } else if (fuse_stats) {
-                if constexpr (sizeof(T) == 2)
-                    k_analyze_v3<DT, false, true><<<wgrid, 256, 0, st>>>(raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(),
-                                                                         ctx->window.as<float>(), dana, wtab, nwaves);
-            } else if (st2) {
-                k_analyze_v3<DT, false, false, true><<<wgrid, 256, 0, st>>>(raster, P, dtiles, dnorms,
-                                                                             ctx->luts.as<int16_t>(),
-                                                                             ctx->window.as<float>(), dana, wtab, nwaves);
-            } else {
-                k_analyze_v3<DT, false><<<wgrid, 256, 0, st>>>(raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(),
-                                                                ctx->window.as<float>(), dana, wtab, nwaves);
-            }
-            if (st2)
-                k_analyze_v3<DT, true, false, true><<<wgrid, 256, 0, st>>>(raster, P, dtiles, dnorms,
-                                                                            ctx->luts.as<int16_t>(),
-                                                                            ctx->window.as<float>(), dana, wtab, nwaves);
-            else
-                k_analyze_v3<DT, true><<<wgrid, 256, 0, st>>>(raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(),
-                                                               ctx->window.as<float>(), dana, wtab, nwaves);
-            prof_end(ctx, "analyze", ev);
-            if (!geo_hit) {  // the geometry's device copies are (being) uploaded on this stream: cache them
-                ctx->geo_tiles = tiles;
-                ctx->geo_plist.assign(hplist, hplist + npartial);
-                ctx->geo_nframes = nframes;
-                ctx->geo_ptrs[2] = nullptr;  // the partial list goes up below
-            }
-            ctx->geo_nwaves = nwaves;
-            ctx->geo_key = key;
-            ctx->geo_ptrs[0] = ctx->tiles.ptr;
-            ctx->geo_ptrs[1] = ctx->wave_tab.ptr;
-            ctx->geo_ptrs[3] = ctx->frame_tile.ptr;
-        }
-        // partial last frames: generic analysis + frame coding into compact slots, CRC-16 sealed in place
-        int64_t *dpbytes = ctx->frame_bytes.as<int64_t>();  // [npartial] (< nframes + 1: below err_flag)
-        if (npartial > 0) {
-            prof_begin(ctx, "partial", &ev);
-            FRS_HIP(ctx->plist.ensure(sizeof(int64_t) * (size_t)npartial));
-            if (!(dev_tiles && ctx->geo_ptrs[2] == ctx->plist.ptr))
-                FRS_HIP(hipMemcpyAsync(ctx->plist.ptr, hplist, sizeof(int64_t) * (size_t)npartial,
-                                       hipMemcpyHostToDevice, st));
-            ctx->geo_ptrs[2] = ctx->plist.ptr;
-            FRS_HIP(ctx->slots.ensure((size_t)npartial * P.slot_words * 4));
-            const int64_t *dpl = ctx->plist.as<int64_t>();
-            if (st2) {
-                k_analyze_partial<DT, true><<<dim3((unsigned)npartial, 4u), kPartThreads, 0, st>>>(
-                    raster, P, dtiles, dnorms, ctx->window.as<float>(), dana, dpl);
-                k_encode_frames<DT, true><<<(unsigned)npartial, kEncThreads, 0, st>>>(
-                    raster, P, dtiles, dnorms, dana, ctx->slots.as<uint32_t>(), dpbytes, err_flag, dpl, nullptr,
-                    nullptr, 0);
-            } else {
-                k_analyze_partial<DT><<<dim3((unsigned)npartial, (unsigned)P.nch), kPartThreads, 0, st>>>(
-                    raster, P, dtiles, dnorms, ctx->window.as<float>(), dana, dpl);
-                k_encode_frames<DT><<<(unsigned)npartial, kEncThreads, 0, st>>>(raster, P, dtiles, dnorms, dana,
-                                                                               ctx->slots.as<uint32_t>(), dpbytes,
-                                                                               err_flag, dpl);
-            }
-            k_seal_partial<<<(unsigned)npartial, 256, 0, st>>>(ctx->slots.as<uint32_t>(), P.slot_words, dpbytes,
-                                                               npartial);
-            prof_end(ctx, "partial", ev);
-        }
-        uint64_t *dstatus = ctx->status.as<uint64_t>();
-        int *ticket = reinterpret_cast<int *>(dstatus + nframes);
-        if (mc) {
-            const int64_t nsub = nframes * P.nvch;
-            FRS_HIP(ctx->sub_slots.ensure(sizeof(uint32_t) * (size_t)nsub * kSubWords));
-            FRS_HIP(ctx->sub_bits.ensure(sizeof(int32_t) * (size_t)nsub));
-            FRS_HIP(ctx->mc_bytes.ensure(sizeof(int64_t) * (size_t)(nframes + 1)));
-            FRS_HIP(hipMemsetAsync(ticket, 0, 2 * sizeof(int), st));
-            uint32_t *dsub = ctx->sub_slots.as<uint32_t>();
-            int32_t *dsbits = ctx->sub_bits.as<int32_t>();
-            int64_t *dmcb = ctx->mc_bytes.as<int64_t>();
-            int32_t *dsest = nullptr;
-            int8_t *dpick = nullptr;
-            if (st2) {
-                FRS_HIP(ctx->sub_est.ensure(sizeof(int32_t) * (size_t)nsub));
-                FRS_HIP(ctx->st_pick.ensure((size_t)nframes + 64));
-                dsest = ctx->sub_est.as<int32_t>();
-                dpick = ctx->st_pick.as<int8_t>();
-            }
-            prof_begin(ctx, "encode", &ev);
-            // (one occupancy query per kernel instantiation; the same gfx950 target for every device)
-            auto launch = [&](auto kern, int &nwg_max, int64_t units, int *tk) {
-                if (nwg_max == 0) FRS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nwg_max, kern, 256, 0));
-                int64_t grid = (int64_t)std::max(1, nwg_max) * ctx->num_cus;
-                grid = std::min<int64_t>(grid, (units + 3) / 4);
-                kern<<<(unsigned)grid, 256, 0, st>>>(
-                    raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(), dana, reinterpret_cast<uint8_t *>(arena_dev),
-                    arena_cap, ctx->frame_off.as<int64_t>(), dstatus, tk, err_flag, ctx->frame_tile.as<int32_t>(),
-                    ctx->hdr_tab.as<uint4>(), 0, ctx->slots.as<uint32_t>(), dpbytes, dsub, dsbits, dsest);
-                return FRS_OK;
-            };
-            if (st2) {  // left, right, mid (16-bit) in one launch; the 17-bit side signals in another
-                static int nwg_lrm = 0, nwg_side = 0;
-                if (int rc2 = launch(k_encode_v4<DT, true, true, false>, nwg_lrm, nframes * 3, ticket)) return rc2;
-                if (int rc2 = launch(k_encode_v4<DT, true, true, true>, nwg_side, nframes, ticket + 1)) return rc2;
-            } else {
-                static int nwg_mc = 0;
-                if (int rc2 = launch(k_encode_v4<DT, true>, nwg_mc, nsub, ticket)) return rc2;
-            }
-            k_mc_frame_bytes<<<(unsigned)((nframes + 255) / 256), 256, 0, st>>>(P, dtiles, ctx->frame_tile.as<int32_t>(),
-                                                                               dsbits, dpbytes, dmcb, err_flag, dsest,
-                                                                               dpick);
-            prof_end(ctx, "encode", ev);
-            k_scan_sizes<<<1, kScanThreads, 0, st>>>(dmcb, ctx->frame_off.as<int64_t>(), nframes);
-            int64_t total = 0;
-            int errv = 0;
-            FRS_HIP(hipMemcpyAsync(&total, ctx->frame_off.as<int64_t>() + nframes, sizeof(int64_t),
-                                   hipMemcpyDeviceToHost, st));
-            FRS_HIP(hipMemcpyAsync(&errv, err_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-            FRS_HIP(hipStreamSynchronize(st));
-            if (errv) {
-                ctx->err = "fast encode declined, flags " + std::to_string(errv);
-                return kFastDeclined;
-            }
-            if (total > arena_cap) {
-                tile_off[ntiles] = total;
-                ctx->err = "arena too small";
-                return FRS_E_NOSPACE;
-            }
-            const size_t mc_lds = sizeof(uint32_t) * (size_t)(P.nch * kFrameWordsV3 + 16);  // <= 70 KB (8 channels)
-            FRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mc_assemble),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)mc_lds));
-            prof_begin(ctx, "assemble", &ev);
-            k_mc_assemble<<<(unsigned)nframes, 256, mc_lds, st>>>(
-                P, dtiles, ctx->frame_tile.as<int32_t>(), dsub, dsbits, ctx->slots.as<uint32_t>(), dpbytes,
-                ctx->frame_off.as<int64_t>(), reinterpret_cast<uint8_t *>(arena_dev), dpick);
-            prof_end(ctx, "assemble", ev);
-            k_gather_tile_off<<<(ntiles + 1 + 255) / 256, 256, 0, st>>>(ctx->frame_off.as<int64_t>(), dtiles, ntiles,
-                                                                       total, ctx->tile_sizes.as<int64_t>());
-            std::vector<TileNorm> hn(ntiles);
-            FRS_HIP(hipMemcpyAsync(tile_off, ctx->tile_sizes.ptr, sizeof(int64_t) * (ntiles + 1), hipMemcpyDeviceToHost,
-                                   st));
-            FRS_HIP(hipMemcpyAsync(hn.data(), dnorms, sizeof(TileNorm) * ntiles, hipMemcpyDeviceToHost, st));
-            FRS_HIP(hipStreamSynchronize(st));
-            prof_collect(ctx);
-            for (int t = 0; t < ntiles; t++) {
-                tile_min[t] = hn[t].dmin;
-                tile_max[t] = hn[t].dmax;
-            }
-            return FRS_OK;
-        }
-        FRS_HIP(hipMemsetAsync(dstatus, 0, sizeof(uint64_t) * (nframes + 1) + 64, st));  // + the ticket counters
-        // frame-header table by frame number within a stream (fast path: mono, 16-bit, blocksize 4096)
-        int hdr_n = 0;
-        {
-            int32_t maxf = 0;
-            for (const TileGeom &tg : tiles) maxf = std::max(maxf, tg.nframes);
-            hdr_n = std::min<int32_t>(maxf, 1 << 16);
-            if (ctx->hdr_tab_n != hdr_n || ctx->hdr_tab_sr != d->sample_rate) {
-                int src, srx = 0;
-                const int sr = d->sample_rate;
-                switch (sr) {
-                case 88200: src = 1; break;
-                case 176400: src = 2; break;
-                case 192000: src = 3; break;
-                case 8000: src = 4; break;
-                case 16000: src = 5; break;
-                case 22050: src = 6; break;
-                case 24000: src = 7; break;
-                case 32000: src = 8; break;
-                case 44100: src = 9; break;
-                case 48000: src = 10; break;
-                case 96000: src = 11; break;
-                default:
-                    if (sr <= 255000 && sr % 1000 == 0) src = srx = 12;
-                    else if (sr % 10 == 0 && sr / 10 <= 65535) src = srx = 14;
-                    else src = srx = 13;
-                }
-                uint8_t c8t[256];
-                for (int i = 0; i < 256; i++) {
-                    uint8_t c = (uint8_t)i;
-                    for (int k = 0; k < 8; k++) c = (c & 0x80) ? (uint8_t)((c << 1) ^ 0x07) : (uint8_t)(c << 1);
-                    c8t[i] = c;
-                }
-                std::vector<uint32_t> tab((size_t)hdr_n * 4, 0);
-                for (int fk = 0; fk < hdr_n; fk++) {
-                    uint8_t h[16] = {0};
-                    int hb = 0;
-                    h[hb++] = 0xFF;
-                    h[hb++] = 0xF8;
-                    h[hb++] = (uint8_t)((12 << 4) | src);
-                    h[hb++] = (uint8_t)(4 << 1);
-                    const uint32_t v = (uint32_t)fk;
-                    if (v < 0x80) h[hb++] = (uint8_t)v;
-                    else if (v < 0x800) { h[hb++] = (uint8_t)(0xC0 | (v >> 6)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-                    else { h[hb++] = (uint8_t)(0xE0 | (v >> 12)); h[hb++] = (uint8_t)(0x80 | ((v >> 6) & 0x3F)); h[hb++] = (uint8_t)(0x80 | (v & 0x3F)); }
-                    if (srx == 12) h[hb++] = (uint8_t)(sr / 1000);
-                    else if (srx == 13) { h[hb++] = (uint8_t)(sr >> 8); h[hb++] = (uint8_t)sr; }
-                    else if (srx == 14) { h[hb++] = (uint8_t)((sr / 10) >> 8); h[hb++] = (uint8_t)(sr / 10); }
-                    uint8_t c = 0;
-                    for (int i = 0; i < hb; i++) c = c8t[c ^ h[i]];
-                    h[hb++] = c;
-                    for (int w = 0; w < 4; w++)
-                        tab[(size_t)fk * 4 + w] = ((uint32_t)h[4 * w] << 24) | ((uint32_t)h[4 * w + 1] << 16) |
-                                                  ((uint32_t)h[4 * w + 2] << 8) | h[4 * w + 3];
-                    tab[(size_t)fk * 4 + 3] = (tab[(size_t)fk * 4 + 3] & 0xFFFFFF00u) | (uint32_t)hb;
-                }
-                FRS_HIP(ctx->hdr_tab.ensure(sizeof(uint32_t) * tab.size() + 16));
-                FRS_HIP(hipMemcpyAsync(ctx->hdr_tab.ptr, tab.data(), sizeof(uint32_t) * tab.size(),
-                                       hipMemcpyHostToDevice, st));
-                FRS_HIP(hipStreamSynchronize(st));
-                ctx->hdr_tab_n = hdr_n;
-                ctx->hdr_tab_sr = d->sample_rate;
-            }
-        }
-        {
-            static int nwg_max = 0;  // (per instantiation; the same gfx950 target for every device)
-            if (nwg_max == 0) FRS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nwg_max, k_encode_v4<DT>, 256, 0));
-            prof_begin(ctx, "encode", &ev);
-            int64_t grid = (int64_t)std::max(1, nwg_max) * ctx->num_cus;
-            grid = std::min<int64_t>(grid, (nframes + 3) / 4);
-            k_encode_v4<DT><<<(unsigned)grid, 256, 0, st>>>(raster, P, dtiles, dnorms, ctx->luts.as<int16_t>(), dana,
-                                                            reinterpret_cast<uint8_t *>(arena_dev), arena_cap,
-                                                            ctx->frame_off.as<int64_t>(), dstatus, ticket, err_flag,
-                                                            ctx->frame_tile.as<int32_t>(), ctx->hdr_tab.as<uint4>(),
-                                                            hdr_n, ctx->slots.as<uint32_t>(), dpbytes);
-            prof_end(ctx, "encode", ev);
-        }
-        FRS_HIP(ctx->host_pack.ensure(res_bytes));
-        int64_t *dpack = ctx->host_pack.as<int64_t>();
-        k_fast_finish<<<(ntiles + 1 + 255) / 256, 256, 0, st>>>(ctx->frame_off.as<int64_t>(), dstatus, dtiles, dnorms,
-                                                               err_flag, ntiles, nframes, dpack);
-        const int64_t *hpack = ctx->pin.at<int64_t>(pin_res);
-        FRS_HIP(hipMemcpyAsync(ctx->pin.at<int64_t>(pin_res), dpack, res_bytes, hipMemcpyDeviceToHost, st));
-        FRS_HIP(hipStreamSynchronize(st));
-        prof_collect(ctx);
-        memcpy(tile_off, hpack, sizeof(int64_t) * (ntiles + 1));
-        const double *mm = reinterpret_cast<const double *>(hpack + ntiles + 1);
-        for (int t = 0; t < ntiles; t++) {
-            tile_min[t] = mm[2 * t];
-            tile_max[t] = mm[2 * t + 1];
-        }
-        const int errv = (int)hpack[3 * (int64_t)ntiles + 1];
-        if (errv & 16) {
-            ctx->err = "arena too small";
-            return FRS_E_NOSPACE;
-        }
-        if (errv) {  // a frame the fast kernels cannot hold (never seen: estimates stay below verbatim)
-            ctx->err = "fast encode declined, flags " + std::to_string(errv);
-            return kFastDeclined;
-        }
+    k_tile_finalize<DT><<<(ntiles + 255) / 256, 256, 0, J.st>>>(J.dnorms, ntiles, J.P.norm_mode, J.P.scale_bits);
+    prof_end(ctx, "stats", ev);
+}
+
+template <int DT, bool SLOW, bool STATS = false, bool ST = false, bool PF = false>
+static void launch_analyze_v3(EncodeJob<DT> &J, int nwaves) {
+    if constexpr (!STATS || sizeof(typename Elem<DT>::T) == 2)  // (fused stats: 16-bit samples only)
+        k_analyze_v3<DT, SLOW, STATS, ST, PF><<<(unsigned)((nwaves + 3) / 4), 256, 0, J.st>>>(
+            J.raster, J.P, J.dtiles, J.dnorms, J.ctx->luts.template as<int16_t>(), J.ctx->window.template as<float>(),
+            J.dana, J.ctx->wave_tab.template as<int2>(), nwaves);
+}
+
+// 2. of the fast paths: LUTs, frame -> tile map, wave table and k_analyze_v3 (lean, then slow tiles); the geometry's
+// device copies go into the cache
+template <int DT>
+static int fast_analyze(EncodeJob<DT> &J, const void *raster_dev) {
+    using T = typename Elem<DT>::T;
+    frs_ctx *ctx = J.ctx;
+    const frs_encode_desc *d = J.d;
+    EncodeParams &P = J.P;
+    hipStream_t st = J.st;
+    const int ntiles = J.ntiles;
+    const std::vector<TileGeom> &tiles = *J.tiles;
+    const bool st2 = J.stereo_fast();
+    const int64_t es = (int64_t)sizeof(T);
+    // alignment class of the 64-sample row segments (tiles whose width is a multiple of 64): the widest of 16,
+    // 8, 4 bytes dividing the band base, the row stride and the tile width in bytes
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(raster_dev) + (size_t)d->band0 * d->band_stride * es;
+    P.vec_ok = align_class(b0, {16, 8, 4}, {d->row_stride * es, (int64_t)d->tile_w * es});
+    FRS_HIP(ctx->luts.ensure(sizeof(int16_t) * (size_t)kLutCap * ntiles));
+    FRS_HIP(ctx->status.ensure(sizeof(uint64_t) * (J.nframes + 1) + 64));
+    if (!J.fuse_stats) k_build_lut<DT><<<ntiles, 256, 0, st>>>(J.dnorms, ctx->luts.as<int16_t>());
+    FRS_HIP(ctx->frame_tile.ensure(sizeof(int32_t) * J.nframes));
+    if (!(J.dev_tiles && ctx->geo.dev_frame_tile == ctx->frame_tile.ptr))
+        k_frame_tile<<<ntiles, 64, 0, st>>>(J.dtiles, ntiles, ctx->frame_tile.as<int32_t>());
+    // wave table: (tile, first frame) per wave, up to 64 frames of one tile each
+    int nwaves = ctx->geo.nwaves;
+    if (!(J.dev_tiles && ctx->geo.dev_wave_tab == ctx->wave_tab.ptr)) {
+        int2 *wt = ctx->pin.at<int2>(J.pin_wt);
+        nwaves = 0;
+        for (int ti = 0; ti < ntiles; ti++)
+            for (int c = 0; c < P.nvch; c++)  // (tile, first frame | coded signal << 24)
+                for (int k0 = 0; k0 < tiles[ti].nframes; k0 += 64) wt[nwaves++] = make_int2(ti, k0 | (c << 24));
+        FRS_HIP(ctx->wave_tab.ensure(sizeof(int2) * nwaves));
+        FRS_HIP(hipMemcpyAsync(ctx->wave_tab.ptr, wt, sizeof(int2) * nwaves, hipMemcpyHostToDevice, st));
+    }
+    hipEvent_t ev;
+    prof_begin(ctx, "analyze", &ev);
+    // small jobs with fused stats (C3): the prefetching form (FRS_ANA_PF=0/1 forces either).  Measured (round 6,
+    // one box): C3 analysis 0.348 -> 0.322 ms; the Sentinel-2 example's separate-stats launch 0.529 -> 0.620 ms
+    // and C4 1.30 -> 1.31-1.33 ms, so those keep the plain form.
+    // (Read per call, unlike the switches frs_create reads once: the tests flip it between two encodes on one
+    // context.)
+    const char *pf_env = getenv("FRS_ANA_PF");
+    const bool pf = !st2 && (pf_env ? atoi(pf_env) == 1 : J.fuse_stats && nwaves <= kPfMaxWaves);
+    if (pf && J.fuse_stats) launch_analyze_v3<DT, false, true, false, true>(J, nwaves);
+    else if (pf) launch_analyze_v3<DT, false, false, false, true>(J, nwaves);
+    else if (J.fuse_stats) launch_analyze_v3<DT, false, true>(J, nwaves);
+    else if (st2) launch_analyze_v3<DT, false, false, true>(J, nwaves);
+    else launch_analyze_v3<DT, false>(J, nwaves);
+    if (st2) launch_analyze_v3<DT, true, false, true>(J, nwaves);
+    else launch_analyze_v3<DT, true>(J, nwaves);
+    prof_end(ctx, "analyze", ev);
+    if (!J.geo_hit) {  // the geometry's device copies are (being) uploaded on this stream: cache them
+        ctx->geo.tiles = tiles;
+        ctx->geo.plist.assign(J.hplist, J.hplist + J.npartial);
+        ctx->geo.nframes = J.nframes;
+        ctx->geo.dev_plist = nullptr;  // the partial list goes up in fast_partial_frames
+    }
+    ctx->geo.nwaves = nwaves;
+    ctx->geo.key = J.key;
+    ctx->geo.dev_tiles = ctx->tiles.ptr;
+    ctx->geo.dev_wave_tab = ctx->wave_tab.ptr;
+    ctx->geo.dev_frame_tile = ctx->frame_tile.ptr;
+    return FRS_OK;
+}
+
+// The fast paths' partial last frames: generic analysis + frame coding into compact slots (ctx->slots, sizes in
+// dpbytes[npartial]), CRC-16 sealed in place
+template <int DT>
+static int fast_partial_frames(EncodeJob<DT> &J, int64_t *dpbytes) {
+    frs_ctx *ctx = J.ctx;
+    const EncodeParams &P = J.P;
+    hipStream_t st = J.st;
+    const int64_t npartial = J.npartial;
+    if (npartial == 0) return FRS_OK;
+    hipEvent_t ev;
+    prof_begin(ctx, "partial", &ev);
+    FRS_HIP(ctx->plist.ensure(sizeof(int64_t) * (size_t)npartial));
+    if (!(J.dev_tiles && ctx->geo.dev_plist == ctx->plist.ptr))
+        FRS_HIP(hipMemcpyAsync(ctx->plist.ptr, J.hplist, sizeof(int64_t) * (size_t)npartial, hipMemcpyHostToDevice, st));
+    ctx->geo.dev_plist = ctx->plist.ptr;
+    FRS_HIP(ctx->slots.ensure((size_t)npartial * P.slot_words * 4));
+    const int64_t *dpl = ctx->plist.as<int64_t>();
+    const float *win = ctx->window.as<float>();
+    uint32_t *dslots = ctx->slots.as<uint32_t>();
+    // one work-group row per coded signal (nvch: the channels, or L / R / M / S of a two-channel stream)
+    const auto analyze = J.stereo_fast() ? k_analyze_partial<DT, true> : k_analyze_partial<DT>;
+    const auto encode = J.stereo_fast() ? k_encode_frames<DT, true> : k_encode_frames<DT>;
+    analyze<<<dim3((unsigned)npartial, (unsigned)P.nvch), kPartThreads, 0, st>>>(J.raster, P, J.dtiles, J.dnorms, win,
+                                                                                J.dana, dpl);
+    encode<<<(unsigned)npartial, kEncThreads, 0, st>>>(J.raster, P, J.dtiles, J.dnorms, J.dana, dslots, dpbytes,
+                                                       J.err_flag, dpl, nullptr, nullptr, 0);
+    k_seal_partial<<<(unsigned)npartial, 256, 0, st>>>(dslots, P.slot_words, dpbytes, npartial);
+    prof_end(ctx, "partial", ev);
+    return FRS_OK;
+}
+
+// 4. and 5. of the paths that size their frames before placing them (generic, multi-channel, stereo): offsets from
+// the frame sizes (frame_off[nframes] = total), error flag and space check on the host, `place` writes the frames at
+// their offsets, then the tile offsets and min/max go back to the host.
+template <int DT, typename Place>
+static int place_and_report(EncodeJob<DT> &J, const int64_t *frame_sizes, int err_rc, const char *err_text,
+                            Place &&place) {
+    frs_ctx *ctx = J.ctx;
+    hipStream_t st = J.st;
+    const int ntiles = J.ntiles;
+    int64_t *dfoff = ctx->frame_off.as<int64_t>();
+    k_scan_sizes<<<1, kScanThreads, 0, st>>>(frame_sizes, dfoff, J.nframes);
+    int64_t total = 0;
+    int errv = 0;
+    FRS_HIP(hipMemcpyAsync(&total, dfoff + J.nframes, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    FRS_HIP(hipMemcpyAsync(&errv, J.err_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    FRS_HIP(hipStreamSynchronize(st));
+    if (errv) {
+        ctx->err = err_text + std::to_string(errv);
+        return err_rc;
+    }
+    if (total > J.arena_cap) {
+        J.tile_off[ntiles] = total;
+        ctx->err = "arena too small";
+        return FRS_E_NOSPACE;
+    }
+    if (const int rc = place()) return rc;
+    k_gather_tile_off<<<(ntiles + 1 + 255) / 256, 256, 0, st>>>(dfoff, J.dtiles, ntiles, total,
+                                                               ctx->tile_sizes.as<int64_t>());
+    std::vector<TileNorm> hn(ntiles);
+    FRS_HIP(hipMemcpyAsync(J.tile_off, ctx->tile_sizes.ptr, sizeof(int64_t) * (ntiles + 1), hipMemcpyDeviceToHost, st));
+    FRS_HIP(hipMemcpyAsync(hn.data(), J.dnorms, sizeof(TileNorm) * ntiles, hipMemcpyDeviceToHost, st));
+    FRS_HIP(hipStreamSynchronize(st));
+    prof_collect(ctx);
+    for (int t = 0; t < ntiles; t++) {
+        J.tile_min[t] = hn[t].dmin;
+        J.tile_max[t] = hn[t].dmax;
+    }
+    return FRS_OK;
+}
+
+// Frame-header table of the mono fast path by frame number within a stream (16-bit, blocksize 4096): 16 bytes per
+// frame number, the header's big-endian words with its length in the last byte (a header here has at most
+// 4 + 3 + 2 + 1 = 10 bytes).  hdr_n is the table's length: k_encode_v4 packs the header itself for fk >= hdr_n.
+constexpr int kHdrTabMax = 1 << 16;  // (1 MB of table; frame numbers of at most 3 UTF-8 bytes)
+static int ensure_header_table(frs_ctx *ctx, const std::vector<TileGeom> &tiles, int sample_rate, int &hdr_n) {
+    int32_t maxf = 0;
+    for (const TileGeom &tg : tiles) maxf = std::max(maxf, tg.nframes);
+    hdr_n = std::min<int32_t>(maxf, kHdrTabMax);
+    if (ctx->hdr_tab_n == hdr_n && ctx->hdr_tab_sr == sample_rate) return FRS_OK;
+    std::vector<uint32_t> tab((size_t)hdr_n * 4, 0);
+    for (int fk = 0; fk < hdr_n; fk++) {
+        uint8_t h[16] = {0};
+        const int hb = frame_header(h, 4096, sample_rate, 16, 0, (uint32_t)fk, host_crc8());
+        uint32_t *row = &tab[(size_t)fk * 4];
+        for (int w = 0; w < 4; w++)
+            row[w] = ((uint32_t)h[4 * w] << 24) | ((uint32_t)h[4 * w + 1] << 16) | ((uint32_t)h[4 * w + 2] << 8) | h[4 * w + 3];
+        row[3] = (row[3] & 0xFFFFFF00u) | (uint32_t)hb;
+    }
+    FRS_HIP(ctx->hdr_tab.ensure(sizeof(uint32_t) * tab.size() + 16));
+    FRS_HIP(hipMemcpyAsync(ctx->hdr_tab.ptr, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice,
+                           ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->hdr_tab_n = hdr_n;
+    ctx->hdr_tab_sr = sample_rate;
+    return FRS_OK;
+}
+
+// 3. of the mono fast path: k_encode_v4 codes the frames and stores them at offsets it resolves by look-back; the
+// tile offsets, min/max and error flags come back in one packed copy
+template <int DT>
+static int encode_fast_mono(EncodeJob<DT> &J, int64_t *dpbytes) {
+    frs_ctx *ctx = J.ctx;
+    hipStream_t st = J.st;
+    const int ntiles = J.ntiles;
+    const int64_t nframes = J.nframes;
+    uint64_t *dstatus = ctx->status.as<uint64_t>();
+    int *ticket = reinterpret_cast<int *>(dstatus + nframes);
+    FRS_HIP(hipMemsetAsync(dstatus, 0, sizeof(uint64_t) * (nframes + 1) + 64, st));  // + the ticket counters
+    int hdr_n = 0;
+    if (const int rc = ensure_header_table(ctx, *J.tiles, J.d->sample_rate, hdr_n)) return rc;
+    hipEvent_t ev;
+    static int nwg_max = 0;
+    prof_begin(ctx, "encode", &ev);
+    if (const int rc = launch_resident(ctx, k_encode_v4<DT>, nwg_max, nframes, J.raster, J.P, J.dtiles, J.dnorms,
+                                       ctx->luts.as<int16_t>(), J.dana, J.arena, J.arena_cap,
+                                       ctx->frame_off.as<int64_t>(), dstatus, ticket, J.err_flag,
+                                       ctx->frame_tile.as<int32_t>(), ctx->hdr_tab.as<uint4>(), hdr_n,
+                                       ctx->slots.as<uint32_t>(), dpbytes, nullptr, nullptr, nullptr))
+        return rc;
+    prof_end(ctx, "encode", ev);
+    FRS_HIP(ctx->host_pack.ensure(J.res_bytes));
+    int64_t *dpack = ctx->host_pack.as<int64_t>();
+    k_fast_finish<<<(ntiles + 1 + 255) / 256, 256, 0, st>>>(ctx->frame_off.as<int64_t>(), dstatus, J.dtiles, J.dnorms,
+                                                           J.err_flag, ntiles, nframes, dpack);
+    const int64_t *hpack = ctx->pin.at<int64_t>(J.pin_res);
+    FRS_HIP(hipMemcpyAsync(ctx->pin.at<int64_t>(J.pin_res), dpack, J.res_bytes, hipMemcpyDeviceToHost, st));
+    FRS_HIP(hipStreamSynchronize(st));
+    prof_collect(ctx);
+    memcpy(J.tile_off, hpack, sizeof(int64_t) * (ntiles + 1));
+    const double *mm = reinterpret_cast<const double *>(hpack + ntiles + 1);
+    for (int t = 0; t < ntiles; t++) {
+        J.tile_min[t] = mm[2 * t];
+        J.tile_max[t] = mm[2 * t + 1];
+    }
+    const int errv = (int)hpack[3 * (int64_t)ntiles + 1];
+    if (errv & 16) {
+        ctx->err = "arena too small";
+        return FRS_E_NOSPACE;
+    }
+    if (errv) {  // a frame the fast kernels cannot hold (never seen: estimates stay below verbatim)
+        ctx->err = "fast encode declined, flags " + std::to_string(errv);
+        return kFastDeclined;
+    }
+    return FRS_OK;
+}
+
+// 3. of the multi-channel and stereo fast paths: k_encode_v4 codes subframes into slots, k_mc_frame_bytes sizes the
+// frames (stereo: picks the channel assignment), k_mc_assemble joins them at their offsets
+template <int DT>
+static int encode_fast_multi(EncodeJob<DT> &J, int64_t *dpbytes) {
+    frs_ctx *ctx = J.ctx;
+    const EncodeParams &P = J.P;
+    hipStream_t st = J.st;
+    const int64_t nframes = J.nframes;
+    const bool st2 = J.stereo_fast();
+    uint64_t *dstatus = ctx->status.as<uint64_t>();
+    int *ticket = reinterpret_cast<int *>(dstatus + nframes);
+    const int64_t nsub = nframes * P.nvch;
+    FRS_HIP(ctx->sub_slots.ensure(sizeof(uint32_t) * (size_t)nsub * kSubWords));
+    FRS_HIP(ctx->sub_bits.ensure(sizeof(int32_t) * (size_t)nsub));
+    FRS_HIP(ctx->mc_bytes.ensure(sizeof(int64_t) * (size_t)(nframes + 1)));
+    FRS_HIP(hipMemsetAsync(ticket, 0, 2 * sizeof(int), st));
+    uint32_t *dsub = ctx->sub_slots.as<uint32_t>();
+    int32_t *dsbits = ctx->sub_bits.as<int32_t>();
+    int64_t *dmcb = ctx->mc_bytes.as<int64_t>();
+    int32_t *dsest = nullptr;
+    int8_t *dpick = nullptr;
+    if (st2) {
+        FRS_HIP(ctx->sub_est.ensure(sizeof(int32_t) * (size_t)nsub));
+        FRS_HIP(ctx->st_pick.ensure((size_t)nframes + 64));
+        dsest = ctx->sub_est.as<int32_t>();
+        dpick = ctx->st_pick.as<int8_t>();
+    }
+    const int32_t *dftile = ctx->frame_tile.as<int32_t>();
+    hipEvent_t ev;
+    prof_begin(ctx, "encode", &ev);
+    auto launch = [&](auto kern, int &nwg_max, int64_t units, int *tk) {
+        return launch_resident(ctx, kern, nwg_max, units, J.raster, P, J.dtiles, J.dnorms, ctx->luts.as<int16_t>(),
+                               J.dana, J.arena, J.arena_cap, ctx->frame_off.as<int64_t>(), dstatus, tk, J.err_flag,
+                               dftile, ctx->hdr_tab.as<uint4>(), 0, ctx->slots.as<uint32_t>(), dpbytes, dsub, dsbits,
+                               dsest);
+    };
+    if (st2) {  // left, right, mid (16-bit) in one launch; the 17-bit side signals in another
+        static int nwg_lrm = 0, nwg_side = 0;
+        if (const int rc = launch(k_encode_v4<DT, true, true, false>, nwg_lrm, nframes * 3, ticket)) return rc;
+        if (const int rc = launch(k_encode_v4<DT, true, true, true>, nwg_side, nframes, ticket + 1)) return rc;
+    } else {
+        static int nwg_mc = 0;
+        if (const int rc = launch(k_encode_v4<DT, true>, nwg_mc, nsub, ticket)) return rc;
+    }
+    k_mc_frame_bytes<<<(unsigned)((nframes + 255) / 256), 256, 0, st>>>(P, J.dtiles, dftile, dsbits, dpbytes, dmcb,
+                                                                       J.err_flag, dsest, dpick);
+    prof_end(ctx, "encode", ev);
+    return place_and_report(J, dmcb, kFastDeclined, "fast encode declined, flags ", [&]() -> int {
+        const size_t mc_lds = sizeof(uint32_t) * (size_t)(P.nch * kFrameWordsV3 + 16);  // <= 70 KB (8 channels)
+        FRS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mc_assemble),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mc_lds));
+        prof_begin(ctx, "assemble", &ev);
+        k_mc_assemble<<<(unsigned)nframes, 256, mc_lds, st>>>(P, J.dtiles, dftile, dsub, dsbits,
+                                                              ctx->slots.as<uint32_t>(), dpbytes,
+                                                              ctx->frame_off.as<int64_t>(), J.arena, dpick);
+        prof_end(ctx, "assemble", ev);
         return FRS_OK;
-    }
+    });
+}
+
+// The generic analysis of every coded signal: autocorrelation / fixed / wasted bits (k_analyze; max_lpc 0 in Pa at the
+// subdivide_tukey levels), the wide fixed-predictor totals of 32-bit streams, and at the subdivide_tukey levels the
+// LPC candidates of every window (dcand)
+template <int DT, bool WIDE, bool ST>
+static void launch_generic_analysis(EncodeJob<DT> &J, const EncodeParams &Pa, LpcCand *dcand, const uint8_t *zero) {
+    frs_ctx *ctx = J.ctx;
+    const unsigned agrid = (unsigned)((J.nframes * J.P.nvch + 127) / 128);
+    k_analyze<DT, WIDE, ST><<<agrid, 128, 0, J.st>>>(J.raster, Pa, J.dtiles, J.dnorms, ctx->window.as<float>(), J.dana,
+                                                      nullptr, 0, zero);
+    if constexpr (WIDE) k_analyze_fixed_wide<DT, ST><<<agrid, 128, 0, J.st>>>(J.raster, Pa, J.dtiles, J.dnorms, J.dana, zero);
+    if (dcand)
+        k_analyze_lpc_hi<DT, WIDE, ST><<<agrid, 128, 0, J.st>>>(J.raster, J.P, J.dtiles, J.dnorms,
+                                                                 ctx->window_hi.as<float>(), J.dana, dcand, J.lv.parts);
+}
+
+// 2. to 5. of the generic path
+template <int DT>
+static int encode_generic(EncodeJob<DT> &J, const void *raster_dev) {
+    using T = typename Elem<DT>::T;
+    frs_ctx *ctx = J.ctx;
+    const frs_encode_desc *d = J.d;
+    const EncodeParams &P = J.P;
+    hipStream_t st = J.st;
+    const int64_t nframes = J.nframes;
     FRS_HIP(ctx->slots.ensure((size_t)nframes * P.slot_words * 4));
     // 2. analysis (lane = coded signal: channel, or L/R/M/S of a two-channel stream).  subdivide_tukey levels: the
     //    fixed-predictor / wasted-bits analysis first (max_lpc 0), then the LPC candidates of every window
     const int64_t nsub = nframes * P.nvch;
     const bool stereo = P.nvch == 4 && P.nch == 2;
-    const unsigned agrid = (unsigned)((nsub + 127) / 128);
+    const bool wide = P.bps > 16;
     EncodeParams Pa = P;
     LpcCand *dcand = nullptr;
     if (P.ncand > 0) {
         Pa.max_lpc = 0;
         FRS_HIP(ctx->lpc_cand.ensure(sizeof(LpcCand) * (size_t)nsub * (size_t)P.ncand));
         dcand = ctx->lpc_cand.as<LpcCand>();
-        if (ctx->window_hi_bs != d->blocksize || ctx->window_hi_parts != lv.parts) {
+        if (ctx->window_hi_bs != d->blocksize || ctx->window_hi_parts != J.lv.parts) {
             // subdivide_tukey(parts): FLAC__stream_encoder_set_apodization stores p / parts, the window is
             // FLAC__window_tukey(p / parts) (float p = 0.5f)
-            std::vector<float> win(d->blocksize, 1.0f);
-            const float pw = 0.5f / (float)lv.parts;
-            const int L = d->blocksize;
-            const int Np = (int)(pw / 2.0f * (float)L) - 1;
-            if (Np > 0)
-                for (int k = 0; k <= Np; k++) {
-                    win[k] = (float)(0.5f - 0.5f * cos(M_PI * k / Np));
-                    win[L - Np - 1 + k] = (float)(0.5f - 0.5f * cos(M_PI * (k + Np) / Np));
-                }
-            FRS_HIP(ctx->window_hi.ensure(sizeof(float) * L));
-            FRS_HIP(hipMemcpyAsync(ctx->window_hi.ptr, win.data(), sizeof(float) * L, hipMemcpyHostToDevice, st));
-            FRS_HIP(hipStreamSynchronize(st));
+            if (const int rc = upload_window(ctx, ctx->window_hi, d->blocksize, 0.5f / (float)J.lv.parts)) return rc;
             ctx->window_hi_bs = d->blocksize;
-            ctx->window_hi_parts = lv.parts;
+            ctx->window_hi_parts = J.lv.parts;
         }
     }
+    hipEvent_t ev;
     prof_begin(ctx, "analyze", &ev);
     uint8_t *zero = nullptr;  // raw-frames tiles: all-zero subframe flags (k_zero_subframes)
-    if (P.bps > 16) {
-        if (stereo) {
-            k_analyze<DT, true, true><<<agrid, 128, 0, st>>>(raster, Pa, dtiles, dnorms, ctx->window.as<float>(), dana,
-                                                                nullptr, 0);
-            k_analyze_fixed_wide<DT, true><<<agrid, 128, 0, st>>>(raster, Pa, dtiles, dnorms, dana);
-            if (dcand)
-                k_analyze_lpc_hi<DT, true, true><<<agrid, 128, 0, st>>>(raster, P, dtiles, dnorms,
-                                                                        ctx->window_hi.as<float>(), dana, dcand, lv.parts);
-        } else {
-            // raw-frames tiles: all-zero subframes analysed by a coalesced pass, skipped by the lane walks
-            if (!dcand) {
-                FRS_HIP(ctx->zero_sub.ensure((size_t)nsub + 64));
-                zero = ctx->zero_sub.as<uint8_t>();
-                EncodeParams Pz = Pa;  // 64-sample row segments: the widest load every band's rows allow
-                const int es = (int)sizeof(T);
-                const uintptr_t b0 = reinterpret_cast<uintptr_t>(raster_dev) + (size_t)d->band0 * d->band_stride * es;
-                Pz.vec_ok = 0;
-                for (int a : {16, 8, 4})
-                    if (Pz.vec_ok == 0 && (d->row_stride * es) % a == 0 && (d->band_stride * es) % a == 0 &&
-                        b0 % a == 0 && ((int64_t)d->tile_w * es) % a == 0)
-                        Pz.vec_ok = a;
-                k_zero_subframes<DT><<<(unsigned)((nsub + 3) / 4), 256, 0, st>>>(raster, Pz, dtiles, dnorms, dana, zero);
-            }
-            k_analyze<DT, true><<<agrid, 128, 0, st>>>(raster, Pa, dtiles, dnorms, ctx->window.as<float>(), dana,
-                                                         nullptr, 0, zero);
-            k_analyze_fixed_wide<DT><<<agrid, 128, 0, st>>>(raster, Pa, dtiles, dnorms, dana, zero);
-            if (dcand)
-                k_analyze_lpc_hi<DT, true><<<agrid, 128, 0, st>>>(raster, P, dtiles, dnorms, ctx->window_hi.as<float>(),
-                                                                  dana, dcand, lv.parts);
-        }
-    } else {
-        if (stereo) {
-            k_analyze<DT, false, true><<<agrid, 128, 0, st>>>(raster, Pa, dtiles, dnorms, ctx->window.as<float>(), dana,
-                                                                 nullptr, 0);
-            if (dcand)
-                k_analyze_lpc_hi<DT, false, true><<<agrid, 128, 0, st>>>(raster, P, dtiles, dnorms,
-                                                                         ctx->window_hi.as<float>(), dana, dcand,
-                                                                         lv.parts);
-        } else {
-            k_analyze<DT, false><<<agrid, 128, 0, st>>>(raster, Pa, dtiles, dnorms, ctx->window.as<float>(), dana,
-                                                          nullptr, 0);
-            if (dcand)
-                k_analyze_lpc_hi<DT, false><<<agrid, 128, 0, st>>>(raster, P, dtiles, dnorms, ctx->window_hi.as<float>(),
-                                                                   dana, dcand, lv.parts);
-        }
+    if (wide && !stereo && !dcand) {
+        // raw-frames tiles: all-zero subframes analysed by a coalesced pass, skipped by the lane walks
+        FRS_HIP(ctx->zero_sub.ensure((size_t)nsub + 64));
+        zero = ctx->zero_sub.as<uint8_t>();
+        EncodeParams Pz = Pa;  // 64-sample row segments: the widest load every band's rows allow
+        const int64_t es = (int64_t)sizeof(T);
+        const uintptr_t b0 = reinterpret_cast<uintptr_t>(raster_dev) + (size_t)d->band0 * d->band_stride * es;
+        Pz.vec_ok = align_class(b0, {16, 8, 4}, {d->row_stride * es, d->band_stride * es, (int64_t)d->tile_w * es});
+        k_zero_subframes<DT><<<(unsigned)((nsub + 3) / 4), 256, 0, st>>>(J.raster, Pz, J.dtiles, J.dnorms, J.dana, zero);
     }
+    if (wide && stereo) launch_generic_analysis<DT, true, true>(J, Pa, dcand, zero);
+    else if (wide) launch_generic_analysis<DT, true, false>(J, Pa, dcand, zero);
+    else if (stereo) launch_generic_analysis<DT, false, true>(J, Pa, dcand, zero);
+    else launch_generic_analysis<DT, false, false>(J, Pa, dcand, zero);
     prof_end(ctx, "analyze", ev);
     // 3. encode frames into slots (loose mid/side: the group leaders' assignments first)
     prof_begin(ctx, "encode", &ev);
     uint32_t *dslots = ctx->slots.as<uint32_t>();
     int64_t *dfb = ctx->frame_bytes.as<int64_t>();
-    int8_t *dloose = nullptr;
+    int8_t *dloose = nullptr;  // (stays null unless a two-channel stream's mid/side is loose)
+    const auto encode = !stereo ? k_encode_frames<DT> : wide ? k_encode_frames<DT, true, int64_t> : k_encode_frames<DT, true>;
     if (stereo && P.loose_frames > 0) {
         std::vector<int64_t> leaders;
-        for (const TileGeom &tg : tiles)
+        for (const TileGeom &tg : *J.tiles)
             for (int k = 0; k < tg.nframes; k += P.loose_frames) leaders.push_back(tg.frame_base + k);
         FRS_HIP(ctx->loose_assign.ensure(sizeof(int8_t) * (size_t)nframes + 64));
         FRS_HIP(ctx->loose_lead.ensure(sizeof(int64_t) * leaders.size()));
@@ -4880,61 +4733,53 @@ static int run_encode(frs_ctx *ctx, const frs_encode_desc *d, const void *raster
                                hipMemcpyHostToDevice, st));
         dloose = ctx->loose_assign.as<int8_t>();
         const int64_t *dlead = ctx->loose_lead.as<int64_t>();
-        if (P.bps > 16)
-            k_encode_frames<DT, true, int64_t><<<(unsigned)leaders.size(), kEncThreads, 0, st>>>(
-                raster, P, dtiles, dnorms, dana, dslots, dfb, err_flag, dlead, dcand, dloose, 1);
-        else
-            k_encode_frames<DT, true><<<(unsigned)leaders.size(), kEncThreads, 0, st>>>(
-                raster, P, dtiles, dnorms, dana, dslots, dfb, err_flag, dlead, dcand, dloose, 1);
+        encode<<<(unsigned)leaders.size(), kEncThreads, 0, st>>>(J.raster, P, J.dtiles, J.dnorms, J.dana, dslots, dfb,
+                                                                 J.err_flag, dlead, dcand, dloose, 1);
         FRS_HIP(hipStreamSynchronize(st));  // (the leader list's host vector goes out of scope)
     }
-    if (stereo && P.bps > 16)
-        k_encode_frames<DT, true, int64_t><<<(unsigned)nframes, kEncThreads, 0, st>>>(raster, P, dtiles, dnorms, dana,
-                                                                                     dslots, dfb, err_flag, nullptr,
-                                                                                     dcand, dloose, 0);
-    else if (stereo)
-        k_encode_frames<DT, true><<<(unsigned)nframes, kEncThreads, 0, st>>>(raster, P, dtiles, dnorms, dana, dslots,
-                                                                             dfb, err_flag, nullptr, dcand, dloose, 0);
-    else
-        k_encode_frames<DT><<<(unsigned)nframes, kEncThreads, 0, st>>>(raster, P, dtiles, dnorms, dana, dslots, dfb,
-                                                                       err_flag, nullptr, dcand, nullptr, 0);
+    encode<<<(unsigned)nframes, kEncThreads, 0, st>>>(J.raster, P, J.dtiles, J.dnorms, J.dana, dslots, dfb, J.err_flag,
+                                                      nullptr, dcand, dloose, 0);
     if (zero)  // the all-zero frames k_encode_frames left
-        k_zero_frames_emit<<<(unsigned)((nframes + 3) / 4), 256, 0, st>>>(P, dtiles, dana, dslots, dfb);
+        k_zero_frames_emit<<<(unsigned)((nframes + 3) / 4), 256, 0, st>>>(P, J.dtiles, J.dana, dslots, dfb);
     prof_end(ctx, "encode", ev);
-    // 4. offsets (frame_off[nframes] = total)
-    k_scan_sizes<<<1, kScanThreads, 0, st>>>(ctx->frame_bytes.as<int64_t>(), ctx->frame_off.as<int64_t>(), nframes);
-    int64_t total = 0;
-    int errv = 0;
-    FRS_HIP(hipMemcpyAsync(&total, ctx->frame_off.as<int64_t>() + nframes, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    FRS_HIP(hipMemcpyAsync(&errv, err_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    FRS_HIP(hipStreamSynchronize(st));
-    if (errv) {
-        ctx->err = "frame exceeded its slot (pathological residuals), flag " + std::to_string(errv);
-        return FRS_E_UNSUPPORTED;
+    // 4. offsets, 5. compact + CRC
+    return place_and_report(J, dfb, FRS_E_UNSUPPORTED, "frame exceeded its slot (pathological residuals), flag ",
+                            [&]() -> int {
+                                prof_begin(ctx, "compact", &ev);
+                                k_compact<<<(unsigned)nframes, 256, 0, st>>>(dslots, P.slot_words, dfb,
+                                                                             ctx->frame_off.as<int64_t>(), nframes,
+                                                                             J.arena);
+                                prof_end(ctx, "compact", ev);
+                                return FRS_OK;
+                            });
+}
+
+template <int DT>
+static int run_encode(frs_ctx *ctx, const frs_encode_desc *d, const void *raster_dev, void *arena_dev,
+                      int64_t arena_cap, int64_t *tile_off, double *tile_min, double *tile_max, bool allow_fast) {
+    EncodeJob<DT> J;
+    J.ctx = ctx;
+    J.d = d;
+    J.arena = reinterpret_cast<uint8_t *>(arena_dev);
+    J.arena_cap = arena_cap;
+    J.tile_off = tile_off;
+    J.tile_min = tile_min;
+    J.tile_max = tile_max;
+    if (const int rc = plan_encode(J, raster_dev, allow_fast)) return rc;
+    if (J.ntiles == 0) {
+        tile_off[0] = 0;
+        return FRS_OK;
     }
-    if (total > arena_cap) {
-        tile_off[ntiles] = total;
-        ctx->err = "arena too small";
-        return FRS_E_NOSPACE;
+    if (!J.fuse_stats) run_stats(J);
+    if (J.path == EncodePath::Generic) return encode_generic(J, raster_dev);
+    if constexpr (Elem<DT>::is_float) {
+        return FRS_E_UNSUPPORTED;  // (unreachable: choose_path keeps float rasters generic)
+    } else {
+        if (const int rc = fast_analyze(J, raster_dev)) return rc;
+        int64_t *dpbytes = ctx->frame_bytes.as<int64_t>();  // [npartial] (< nframes + 1: below err_flag)
+        if (const int rc = fast_partial_frames(J, dpbytes)) return rc;
+        return J.path == EncodePath::FastMono ? encode_fast_mono(J, dpbytes) : encode_fast_multi(J, dpbytes);
     }
-    // 5. compact + CRC
-    prof_begin(ctx, "compact", &ev);
-    k_compact<<<(unsigned)nframes, 256, 0, st>>>(ctx->slots.as<uint32_t>(), P.slot_words, ctx->frame_bytes.as<int64_t>(),
-                                                 ctx->frame_off.as<int64_t>(), nframes,
-                                                 reinterpret_cast<uint8_t *>(arena_dev));
-    prof_end(ctx, "compact", ev);
-    k_gather_tile_off<<<(ntiles + 1 + 255) / 256, 256, 0, st>>>(ctx->frame_off.as<int64_t>(), dtiles, ntiles, total,
-                                                               ctx->tile_sizes.as<int64_t>());
-    std::vector<TileNorm> hn(ntiles);
-    FRS_HIP(hipMemcpyAsync(tile_off, ctx->tile_sizes.ptr, sizeof(int64_t) * (ntiles + 1), hipMemcpyDeviceToHost, st));
-    FRS_HIP(hipMemcpyAsync(hn.data(), dnorms, sizeof(TileNorm) * ntiles, hipMemcpyDeviceToHost, st));
-    FRS_HIP(hipStreamSynchronize(st));
-    prof_collect(ctx);
-    for (int t = 0; t < ntiles; t++) {
-        tile_min[t] = hn[t].dmin;
-        tile_max[t] = hn[t].dmax;
-    }
-    return FRS_OK;
 }
 
 template <int DT>

@@ -61,6 +61,19 @@ struct ProfEntry {
     int count = 0;
 };
 
+// Cached job geometry of the fast encode paths: the tile table (partial frames marked), the analysis wave table, the
+// partial-frame list and the frame -> tile map stay on the device while the descriptor's geometry repeats (a bench or
+// a server encoding same-shaped jobs skips their rebuild and uploads).
+struct EncodeGeometry {
+    std::vector<int64_t> key;           // descriptor geometry the cache holds (empty: nothing cached)
+    std::vector<frs::TileGeom> tiles;   // host tile table, partial frames marked
+    std::vector<int64_t> plist;         // partial-frame list
+    int64_t nframes = 0;
+    int nwaves = 0;
+    // the device allocations each table was last uploaded into (a grown DevBuf is a new allocation: upload again)
+    void *dev_tiles = nullptr, *dev_wave_tab = nullptr, *dev_plist = nullptr, *dev_frame_tile = nullptr;
+};
+
 struct frs_ctx {
     int device = 0;
     int num_cus = 256;
@@ -89,15 +102,7 @@ struct frs_ctx {
     std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> ev_pending;
     // cached window (blocksize)
     int window_bs = 0;
-    // cached job geometry of the fast encode path: the tile table (partial frames marked), the analysis wave table,
-    // the partial-frame list and frame -> tile map stay on the device while the descriptor's geometry repeats (a
-    // bench or a server encoding same-shaped jobs skips their rebuild and uploads)
-    std::vector<int64_t> geo_key;      // descriptor geometry the cache holds (empty: nothing cached)
-    std::vector<frs::TileGeom> geo_tiles;  // host tile table, partial frames marked
-    std::vector<int64_t> geo_plist;    // partial-frame list
-    int64_t geo_nframes = 0;
-    int geo_nwaves = 0;
-    void *geo_ptrs[4] = {nullptr, nullptr, nullptr, nullptr};  // tiles, wave_tab, plist, frame_tile as uploaded
+    EncodeGeometry geo;  // cached job geometry of the fast encode paths
     // subdivide_tukey levels (6..8): LPC candidates per coded signal, the tukey(0.5 / parts) window; loose mid/side:
     // per-frame assignment of the group leaders and the leader frame list
     DevBuf lpc_cand, window_hi, loose_assign, loose_lead;
