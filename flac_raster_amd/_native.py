@@ -38,6 +38,7 @@ EXPORTS = (
     "frs_synth_raster_device", "frs_ctx_stream", "frs_profile_enable", "frs_profile_avg_ms",
     "frs_profile_reset", "frs_comm_unique_id", "frs_comm_init", "frs_comm_destroy", "frs_comm_allgather_i64",
     "frs_compare_device", "frs_compare",
+    "frs_place_tiles_device", "frs_decode_tiles_window_device", "frs_decode_tiles_window",
 )
 
 # launch constants of k_compare (csrc/frs_compare.hip: kCmpBlock, kCmpUnroll, kCmpMaxGroups): a work-group step covers
@@ -99,6 +100,35 @@ class CompareBand(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TileWindow(ctypes.Structure):
+    """frs_tile_window: a tile's size and its position relative to the destination raster's origin"""
+    _fields_ = [
+        ("col_off", ctypes.c_int64), ("row_off", ctypes.c_int64),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+    ]
+
+
+class RasterDesc(ctypes.Structure):
+    """frs_raster_desc: a [nbands][height][width] destination raster with element strides"""
+    _fields_ = [
+        ("height", ctypes.c_int64), ("width", ctypes.c_int64),
+        ("row_stride", ctypes.c_int64), ("band_stride", ctypes.c_int64),
+        ("dtype", ctypes.c_int32), ("nbands", ctypes.c_int32),
+    ]
+
+
+def tile_window_array(windows) -> ctypes.Array:
+    """(TileWindow * n) from TileWindow structures or (col_off, row_off, width, height) rows."""
+    if isinstance(windows, ctypes.Array) and windows._type_ is TileWindow:
+        return windows
+    ws = list(windows)
+    arr = (TileWindow * max(len(ws), 1))()
+    for i, w in enumerate(ws):
+        arr[i] = w if isinstance(w, TileWindow) else TileWindow(int(w[0]), int(w[1]), int(w[2]), int(w[3]))
+    arr._n = len(ws)
+    return arr
 
 
 _lib = None
@@ -193,6 +223,14 @@ def load_library(path: Optional[os.PathLike] = None):
         L.frs_compare_device.argtypes = cmp_args
         L.frs_compare.restype = i32
         L.frs_compare.argtypes = cmp_args
+        twp, rdp = ctypes.POINTER(TileWindow), ctypes.POINTER(RasterDesc)
+        L.frs_place_tiles_device.restype = i32
+        L.frs_place_tiles_device.argtypes = [ctxp, rdp, vp, ip64, twp, i32, vp]
+        decw_args = [ctxp, vp, ip64, i32, i32, i32, twp, dp, dp, rdp, vp]
+        L.frs_decode_tiles_window_device.restype = i32
+        L.frs_decode_tiles_window_device.argtypes = decw_args
+        L.frs_decode_tiles_window.restype = i32
+        L.frs_decode_tiles_window.argtypes = decw_args
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -566,6 +604,79 @@ class Context:
         self._check(self.lib.frs_compare_device(self.handle, ctypes.byref(desc), ctypes.c_void_p(a_ptr),
                                                 ctypes.c_void_p(b_ptr), out))
         return [x.as_dict() for x in out] if as_dicts else list(out)
+
+    # ---- placement
+    @staticmethod
+    def make_raster_desc(height, width, dtype, *, nbands=1, row_stride=None, band_stride=None) -> RasterDesc:
+        d = RasterDesc()
+        d.height, d.width, d.nbands = int(height), int(width), int(nbands)
+        d.dtype = DTYPE_CODES[np.dtype(dtype)]
+        d.row_stride = int(width if row_stride is None else row_stride)
+        d.band_stride = int(d.row_stride * d.height if band_stride is None else band_stride)
+        return d
+
+    def place_tiles_device(self, tiles_ptr: int, pcm_off: Sequence[int], windows, desc: RasterDesc, dst_ptr: int,
+                           ntiles: Optional[int] = None) -> None:
+        """frs_place_tiles_device: tile t (windows[t].width * height pixels of desc.nbands interleaved elements, from
+        element pcm_off[t] * nbands of the device buffer at tiles_ptr) goes to its window of the device raster at
+        dst_ptr, clipped to it.  Windows must not overlap inside the destination."""
+        win = tile_window_array(windows)
+        n = int(getattr(win, "_n", len(win)) if ntiles is None else ntiles)
+        poff = np.ascontiguousarray(np.asarray(pcm_off, dtype=np.int64))
+        if n > 0 and len(poff) < n:
+            raise ValueError("one pcm_off per tile")
+        self._check(self.lib.frs_place_tiles_device(
+            self.handle, ctypes.byref(desc), ctypes.c_void_p(tiles_ptr),
+            poff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), win, n, ctypes.c_void_p(dst_ptr)))
+
+    def _window_args(self, stream_off, windows, data_min, data_max):
+        win = tile_window_array(windows)
+        n = int(getattr(win, "_n", len(win)))
+        soff = np.ascontiguousarray(np.asarray(stream_off, dtype=np.int64))
+        mn = np.ascontiguousarray(np.asarray(data_min, dtype=np.float64))
+        mx = np.ascontiguousarray(np.asarray(data_max, dtype=np.float64))
+        if len(soff) != n + 1 or len(mn) != n or len(mx) != n:
+            raise ValueError("one stream offset pair and one data_min/data_max per tile window")
+        dp = ctypes.POINTER(ctypes.c_double)
+        return win, n, soff, soff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), mn, mn.ctypes.data_as(dp), mx, \
+            mx.ctypes.data_as(dp)
+
+    def decode_tiles_window_device(self, blob, stream_off, windows, bps: int, data_min, data_max, dtype, dst,
+                                   dst_shape, *, row_stride=None, band_stride=None, blocksize: int = 4096,
+                                   blob_ptr: Optional[int] = None, dst_ptr: Optional[int] = None) -> RasterDesc:
+        """frs_decode_tiles_window_device: stream s of the device blob is tile s; it is decoded, de-normalised to
+        `dtype` and placed at windows[s] of the (bands, height, width) = dst_shape raster in the DeviceBuffer `dst`
+        (element strides row_stride / band_stride, dense by default).  Returns the raster descriptor used."""
+        nb, h, w = (int(x) for x in dst_shape)
+        d = self.make_raster_desc(h, w, dtype, nbands=nb, row_stride=row_stride, band_stride=band_stride)
+        need = ((nb - 1) * d.band_stride + (h - 1) * d.row_stride + w) * np.dtype(dtype).itemsize
+        if dst_ptr is None and need > dst.nbytes:
+            raise ValueError("destination buffer too small")
+        win, n, soff, soff_p, mn, mn_p, mx, mx_p = self._window_args(stream_off, windows, data_min, data_max)
+        self._check(self.lib.frs_decode_tiles_window_device(
+            self.handle, ctypes.c_void_p(blob.ptr if blob_ptr is None else blob_ptr), soff_p, n, int(bps),
+            int(blocksize), win, mn_p, mx_p, ctypes.byref(d), ctypes.c_void_p(dst.ptr if dst_ptr is None else dst_ptr)))
+        return d
+
+    def decode_tiles_window_host(self, blob, stream_off, windows, bps: int, data_min, data_max, dtype,
+                                 dst_shape=None, out: Optional[np.ndarray] = None, blocksize: int = 4096) -> np.ndarray:
+        """frs_decode_tiles_window: decode the tiles of the host blob into their windows of a (bands, height, width)
+        raster.  `out` (C-contiguous, of `dtype`) is filled in place -- elements no tile covers keep their values -- or a
+        zero-filled array of dst_shape is made and returned."""
+        if out is None:
+            out = np.zeros(tuple(int(x) for x in dst_shape), dtype=dtype)
+        if out.ndim != 3 or not out.flags.c_contiguous or out.dtype != np.dtype(dtype) or not out.flags.writeable:
+            raise ValueError("out must be a writeable C-contiguous (bands, height, width) array of `dtype`")
+        if out.size == 0:
+            raise ValueError("empty raster")
+        b = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+        b = np.ascontiguousarray(b)
+        nb, h, w = out.shape
+        d = self.make_raster_desc(h, w, dtype, nbands=nb)
+        win, n, soff, soff_p, mn, mn_p, mx, mx_p = self._window_args(stream_off, windows, data_min, data_max)
+        self._check(self.lib.frs_decode_tiles_window(self.handle, _p(b), soff_p, n, int(bps), int(blocksize), win, mn_p,
+                                                     mx_p, ctypes.byref(d), _p(out)))
+        return out
 
     # ---- bench helpers
     def synth_raster(self, buf: DeviceBuffer, bands: int, height: int, width: int, row0: int = 0,

@@ -92,9 +92,16 @@ def create_streaming(
     distributed: bool = typer.Option(False, "--distributed",
                                      help="Extension: run as one rank of a launcher (RANK/WORLD_SIZE/LOCAL_RANK/"
                                           "MASTER_ADDR/MASTER_PORT in the environment)"),
+    verify: bool = typer.Option(False, "--verify", help="Extension: read the written file back, decode it into one "
+                                                        "raster on the GPU and compare it with band 1 of the source "
+                                                        "there (single GPU only); exit status 3 when it differs"),
 ):
     """Create Netflix-style streaming FLAC with self-contained tiles"""
     from . import streaming
+    # --verify is checked before anything else is looked at or done
+    if verify and (gpus > 1 or distributed):
+        typer.echo("Error: --verify runs on one GPU: it cannot be combined with --gpus > 1 or --distributed", err=True)
+        raise typer.Exit(1)
     if not input_file.exists():
         typer.echo(f"Error: Input file does not exist: {input_file}", err=True)
         raise typer.Exit(1)
@@ -116,6 +123,7 @@ def create_streaming(
             raise typer.Exit(1)
         typer.echo(f"SUCCESS: {output_file} ({gpus} GPUs)")
         return
+    differs = False
     try:
         if distributed:
             from .distributed import create_streaming_distributed
@@ -123,10 +131,21 @@ def create_streaming(
         else:
             index = streaming.create_streaming(input_file, output_file, tile_size)
         typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles)")
+        if verify:
+            from . import geotiff
+            ex = streaming.verify_streaming(output_file, geotiff.read(input_file).data[0])
+            differs = ex["n_different"] != 0
+            if differs:
+                typer.echo(f"VERIFY: differs (n_different={ex['n_different']}, "
+                           f"max_difference={ex['max_difference']})")
+            else:
+                typer.echo("VERIFY: lossless")
     except Exception as e:
         log.exception("Streaming FLAC creation failed")
         typer.echo(f"Error creating streaming FLAC: {e}", err=True)
         raise typer.Exit(1)
+    if differs:
+        raise typer.Exit(3)
 
 
 @app.command("extract-streaming")
@@ -138,9 +157,14 @@ def extract_streaming(
     center: bool = typer.Option(False, "--center", help="Extract center tile"),
     last: bool = typer.Option(False, "--last", help="Extract last tile"),
     mosaic: bool = typer.Option(False, "--mosaic", help="Extension: mosaic every tile intersecting --bbox"),
+    all_tiles: bool = typer.Option(False, "--all", help="Extension: decode every tile and write the whole raster"),
 ):
     """Extract tiles from Netflix-style streaming FLAC files"""
     from . import streaming
+    # --all takes no tile selection: checked before anything is read
+    if all_tiles and (bbox is not None or tile_id is not None or center or last):
+        typer.echo("Error: --all cannot be combined with --bbox, --tile-id, --center or --last", err=True)
+        raise typer.Exit(1)
     coords = None
     if bbox:
         try:
@@ -151,7 +175,10 @@ def extract_streaming(
             typer.echo(f"Error: Invalid bbox format. Use 'xmin,ymin,xmax,ymax': {e}", err=True)
             raise typer.Exit(1)
     try:
-        if mosaic and coords is not None:
+        if all_tiles:
+            index = streaming.extract_all(flac_url, output)
+            typer.echo(f"SUCCESS: Extracted all {len(index['frames'])} tiles to {output}")
+        elif mosaic and coords is not None:
             from . import geotiff
             arr, win, tr = streaming.extract_bbox_mosaic(flac_url, coords)
             n, index = streaming.read_index(flac_url)

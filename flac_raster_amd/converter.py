@@ -162,11 +162,26 @@ class RasterFLACConverter:
         frames = np.frombuffer(buf, dtype=np.uint8)[sm.audio_offset:]
         dtype = np.dtype(md["dtype"])
         # FileDecoder + WAV round trip + _denormalize_from_audio in one GPU pass (converter.py:241-282)
+        if count > 1:
+            # the interleaved channels go to their band planes on the device (one tile whose window is the raster):
+            # the host receives (count, H, W) as it is, no strided transpose of the whole raster
+            if sm.channels != count:
+                raise ValueError(f"stream has {sm.channels} channels, metadata says {count} bands")
+            ctx = self.ctx
+            blob, dst = ctx.alloc(len(frames) + 16), ctx.alloc(count * H * W * dtype.itemsize)
+            try:
+                blob.upload(frames)
+                ctx.decode_tiles_window_device(blob, [0, len(frames)], [(0, 0, W, H)], sm.bps, [md["data_min"]],
+                                               [md["data_max"]], dtype, dst, (count, H, W), blocksize=sm.blocksize)
+                out = np.empty((count, H, W), dtype=dtype)
+                dst.download(out=out)
+            finally:
+                blob.close()
+                dst.close()
+            return out
         out = self.ctx.decode_tiles_host(frames, [0, len(frames)], [W * H], channels=sm.channels, bps=sm.bps,
                                          data_min=[md["data_min"]], data_max=[md["data_max"]], dtype=dtype,
                                          blocksize=sm.blocksize)
-        if count > 1:
-            return np.ascontiguousarray(out.reshape(H, W, count).transpose(2, 0, 1))
         return out.reshape(1, H, W)
 
     def flac_to_tiff(self, flac_path: Path, tiff_path: Path):

@@ -125,10 +125,11 @@ void frs_ctx_destroy(frs_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->tiles, &ctx->norms, &ctx->analysis, &ctx->slots, &ctx->frame_bytes, &ctx->frame_off,
                       &ctx->window, &ctx->tile_sizes, &ctx->luts, &ctx->status, &ctx->frame_tile, &ctx->hdr_tab, &ctx->wave_tab, &ctx->plist, &ctx->lpc_cand, &ctx->sub_est, &ctx->st_pick, &ctx->window_hi, &ctx->loose_assign, &ctx->loose_lead, &ctx->sub_slots, &ctx->sub_bits, &ctx->mc_bytes, &ctx->raster_stage, &ctx->arena_stage, &ctx->host_pack,
                       &ctx->dec_cand, &ctx->dec_count, &ctx->dec_pcm, &ctx->dec_soff, &ctx->dec_next, &ctx->dec_status, &ctx->dec_fb, &ctx->dec_sel, &ctx->dec_crc,
-                      &ctx->dec_chass, &ctx->cmp_part, &ctx->cmp_stage};
+                      &ctx->dec_chass, &ctx->cmp_part, &ctx->cmp_stage, &ctx->place_tab, &ctx->place_stage};
     for (DevBuf *b : bufs) b->release();
     ctx->pin.release();
     ctx->cmp_pin.release();
+    ctx->place_pin.release();
     ctx->ring[0].release();
     ctx->ring[1].release();
     if (ctx->h2d_stream) hipStreamDestroy(ctx->h2d_stream);
@@ -659,6 +660,117 @@ int frs_compare(frs_ctx *ctx, const frs_compare_desc *desc, const void *a_host, 
     FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, a_host, na, hipMemcpyHostToDevice, ctx->stream));
     FRS_HIP(hipMemcpyAsync(ctx->cmp_stage.ptr, b_host, nb, hipMemcpyHostToDevice, ctx->stream));
     return frs::compare_job(ctx, desc, ctx->raster_stage.ptr, ctx->cmp_stage.ptr, out_host);
+}
+
+}  // extern "C"
+
+// argument checks shared by the placement entry points, before anything is sized, copied or launched
+static int check_place_args(frs_ctx *ctx, const frs_raster_desc *d, const frs_tile_window *win, int32_t ntiles) {
+    if (!d) { ctx->err = "null desc"; return FRS_E_ARG; }
+    if (ntiles < 0) { ctx->err = "place: ntiles < 0"; return FRS_E_ARG; }
+    if (d->height < 1 || d->width < 1) { ctx->err = "place: destination height and width must be >= 1"; return FRS_E_ARG; }
+    if (d->row_stride < d->width) { ctx->err = "row_stride < width"; return FRS_E_ARG; }
+    if (d->nbands < 1 || d->nbands > frs::kMaxChannels) { ctx->err = "nbands must be 1..8 (FLAC channels)"; return FRS_E_ARG; }
+    if (frs::dtype_size(d->dtype) == 0) { ctx->err = "bad dtype"; return FRS_E_ARG; }
+    if (compare_extent(d->height, d->width, d->nbands, d->row_stride, d->nbands > 1 ? d->band_stride : 0) < 0) {
+        ctx->err = "place: raster extent overflows";
+        return FRS_E_ARG;
+    }
+    // (a band must end before the next begins: the extent above, which sizes the host variant's copies, relies on it)
+    if (d->nbands > 1 && d->band_stride < (d->height - 1) * d->row_stride + d->width) {
+        ctx->err = "band_stride too small";
+        return FRS_E_ARG;
+    }
+    if (ntiles > 0 && !win) { ctx->err = "null pointer"; return FRS_E_ARG; }
+    for (int32_t i = 0; i < ntiles; i++) {
+        if (win[i].width < 1 || win[i].height < 1) { ctx->err = "place: tile width and height must be >= 1"; return FRS_E_ARG; }
+        // positions far outside any raster would overflow the clipping arithmetic: such a tile cannot touch the destination
+        if (win[i].col_off < -(INT64_MAX >> 2) || win[i].col_off > (INT64_MAX >> 2) || win[i].row_off < -(INT64_MAX >> 2) ||
+            win[i].row_off > (INT64_MAX >> 2)) {
+            ctx->err = "place: tile offset out of range";
+            return FRS_E_ARG;
+        }
+    }
+    return FRS_OK;
+}
+
+extern "C" {
+
+int frs_place_tiles_device(frs_ctx *ctx, const frs_raster_desc *dst, const void *tiles_dev, const int64_t *pcm_off,
+                           const frs_tile_window *win, int32_t ntiles, void *dst_dev) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_place_args(ctx, dst, win, ntiles)) return rc;
+    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
+    if (!tiles_dev || !dst_dev || reinterpret_cast<uintptr_t>(tiles_dev) % es || reinterpret_cast<uintptr_t>(dst_dev) % es) {
+        ctx->err = "place: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    if (ntiles > 0 && !pcm_off) { ctx->err = "null pointer"; return FRS_E_ARG; }
+    for (int32_t i = 0; i < ntiles; i++)
+        if (pcm_off[i] < 0 || pcm_off[i] > (INT64_MAX >> 8)) { ctx->err = "place: bad pcm_off"; return FRS_E_ARG; }
+    FRS_HIP(hipSetDevice(ctx->device));
+    return frs::place_job(ctx, dst, tiles_dev, pcm_off, win, ntiles, dst_dev);
+}
+
+int frs_decode_tiles_window_device(frs_ctx *ctx, const uint8_t *blob_dev, const int64_t *stream_off, int32_t nstreams,
+                                   int32_t bps, int32_t blocksize, const frs_tile_window *win, const double *data_min,
+                                   const double *data_max, const frs_raster_desc *dst, void *dst_dev) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_place_args(ctx, dst, win, nstreams)) return rc;
+    const size_t es = (size_t)frs::dtype_size(dst->dtype);
+    if (!dst_dev || reinterpret_cast<uintptr_t>(dst_dev) % es) {
+        ctx->err = "place: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    // tile s holds width * height samples per channel, one after the other in the staging buffer
+    std::vector<int64_t> poff((size_t)nstreams + 1, 0);
+    for (int32_t s = 0; s < nstreams; s++) poff[s + 1] = poff[s] + (int64_t)win[s].width * win[s].height;
+    if (poff[nstreams] > (INT64_MAX >> 8)) { ctx->err = "place: too many samples"; return FRS_E_ARG; }
+    FRS_HIP(hipSetDevice(ctx->device));
+    FRS_HIP(ctx->place_stage.ensure((size_t)poff[nstreams] * dst->nbands * es + 16));
+    if (int rc = decode_entry(ctx, blob_dev, stream_off, nstreams, dst->nbands, bps, blocksize, nullptr, poff.data(),
+                              data_min, data_max, dst->dtype, ctx->place_stage.ptr))
+        return rc;
+    return frs::place_job(ctx, dst, ctx->place_stage.ptr, poff.data(), win, nstreams, dst_dev);
+}
+
+int frs_decode_tiles_window(frs_ctx *ctx, const uint8_t *blob_host, const int64_t *stream_off, int32_t nstreams,
+                            int32_t bps, int32_t blocksize, const frs_tile_window *win, const double *data_min,
+                            const double *data_max, const frs_raster_desc *dst, void *dst_host) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_place_args(ctx, dst, win, nstreams)) return rc;
+    if (!blob_host || !dst_host || !stream_off || reinterpret_cast<uintptr_t>(dst_host) % (uintptr_t)frs::dtype_size(dst->dtype)) {
+        ctx->err = "place: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    for (int s = 1; s <= nstreams; s++)
+        if (stream_off[s] < stream_off[s - 1] || stream_off[0] < 0) {
+            ctx->err = "stream and sample offsets must be non-decreasing";
+            return FRS_E_ARG;
+        }
+    FRS_HIP(hipSetDevice(ctx->device));
+    if (nstreams == 0) return FRS_OK;
+    const size_t es = (size_t)frs::dtype_size(dst->dtype);
+    const size_t dbytes = (size_t)compare_extent(dst->height, dst->width, dst->nbands, dst->row_stride,
+                                                 dst->nbands > 1 ? dst->band_stride : 0) * es;
+    const int64_t nbytes = stream_off[nstreams] - stream_off[0];
+    FRS_HIP(ctx->raster_stage.ensure((size_t)nbytes + 16));
+    FRS_HIP(ctx->arena_stage.ensure(dbytes + 16));
+    // the destination goes up first: what no tile covers comes back as it was
+    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
+    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, blob_host + stream_off[0], (size_t)nbytes, hipMemcpyHostToDevice,
+                           ctx->stream));
+    std::vector<int64_t> rel((size_t)nstreams + 1);
+    for (int s = 0; s <= nstreams; s++) rel[s] = stream_off[s] - stream_off[0];
+    if (int rc = frs_decode_tiles_window_device(ctx, ctx->raster_stage.as<uint8_t>(), rel.data(), nstreams, bps, blocksize,
+                                                win, data_min, data_max, dst, ctx->arena_stage.ptr))
+        return rc;
+    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    return FRS_OK;
 }
 
 }  // extern "C"

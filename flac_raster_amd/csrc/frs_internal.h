@@ -112,6 +112,10 @@ struct frs_ctx {
     // compare (frs_compare*): per-work-group partial records, their pinned host copy, the second raster's staging
     DevBuf cmp_part, cmp_stage;
     HostPin cmp_pin;
+    // placement (frs_place_tiles_device, frs_decode_tiles_window*): the tile table and its pinned host copy, the
+    // decoders' interleaved output that frs_decode_tiles_window* places from
+    DevBuf place_tab, place_stage;
+    HostPin place_pin;
     // page-locked host allocations of this context (frs_host_malloc): a C5 decode whose output lies in one returns
     // when the kernel's last work-group has published it, before the stream's completion signal (`unsynced` then
     // makes the next call check the stream for an asynchronous fault first)
@@ -169,4 +173,7 @@ int synth_job(frs_ctx *ctx, int16_t *dev, int bands, int64_t height, int64_t wid
 int dtype_size(int dt);
 // Difference statistics of two device rasters (frs_compare.hip); the descriptor is already validated.
 int compare_job(frs_ctx *ctx, const frs_compare_desc *d, const void *a_dev, const void *b_dev, frs_compare_band *out);
+// Place ntiles decoded tiles into a device raster (frs_place.hip); the arguments are already validated.
+int place_job(frs_ctx *ctx, const frs_raster_desc *d, const void *tiles_dev, const int64_t *pcm_off,
+              const frs_tile_window *win, int32_t ntiles, void *dst_dev);
 }  // namespace frs

@@ -508,27 +508,97 @@ def bbox_pixel_window(transform: geotiff.Affine, bbox: Sequence[float], width: i
     return {"col_off": c0, "row_off": r0, "width": c1 - c0, "height": r1 - r0}
 
 
+def tile_windows(frames: Sequence[Dict], origin: Tuple[int, int] = (0, 0)) -> List[Tuple[int, int, int, int]]:
+    """frs_tile_window rows (col_off, row_off, width, height) of index entries, in their order, relative to the
+    (col, row) origin of a destination window: tiles up or left of the origin get negative offsets (the placement
+    clips them).  Pure host code."""
+    c0, r0 = int(origin[0]), int(origin[1])
+    return [(int(f["window"]["col_off"]) - c0, int(f["window"]["row_off"]) - r0, int(f["window"]["width"]),
+             int(f["window"]["height"])) for f in frames]
+
+
+def decode_into_window(streams: Sequence[bytes], frames: Sequence[Dict], origin: Tuple[int, int],
+                       shape: Tuple[int, int], ctx: Optional[Context] = None):
+    """Decode whole tile streams (one per index entry of `frames`) straight into the (height, width) = shape window
+    whose upper-left pixel is the raster's (col, row) = origin: one batched decode + placement on the device
+    (frs_decode_tiles_window_device), tiles clipped to the window.  Each tile's frame bytes are uploaded to their
+    place in the device blob (the body is never concatenated on the host).  Window pixels no tile covers are zero.
+    Returns (DeviceBuffer holding the (1, height, width) raster, its dtype)."""
+    ctx = ctx or default_context()
+    h, w = int(shape[0]), int(shape[1])
+    metas = [container.parse_metadata(s) for s in streams]
+    mds = [container.read_raster_tags(m) for m in metas]
+    wins = tile_windows(frames, origin)
+    if not streams or len(wins) != len(streams):
+        raise ValueError("one tile stream per index entry")
+    for m, md, win in zip(metas, mds, wins):
+        if md is None:
+            raise ValueError("No metadata found in FLAC file or sidecar file")
+        if m.bps not in (16, 32):
+            raise ValueError("Only int16/int32 data type is supported")
+        if m.channels != 1 or (int(md["width"]), int(md["height"])) != (win[2], win[3]):
+            raise ValueError("a streaming tile is one band of its index window's size")
+    dtype = np.dtype(mds[0]["dtype"])
+    if any(np.dtype(md["dtype"]) != dtype for md in mds):
+        raise ValueError("the tiles of one raster share a dtype")
+    # one decode call per (bps, blocksize); a file written by create-streaming has one group
+    groups: Dict[Tuple[int, int], List[int]] = {}
+    for i, m in enumerate(metas):
+        groups.setdefault((m.bps, m.blocksize), []).append(i)
+    order = [i for idx in groups.values() for i in idx]
+    sizes = [len(streams[i]) - metas[i].audio_offset for i in order]
+    off = np.zeros(len(order) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(sizes)
+    blob = ctx.alloc(int(off[-1]) + 16)
+    dst = ctx.alloc(h * w * dtype.itemsize)
+    try:
+        for k, i in enumerate(order):
+            blob.upload(np.frombuffer(streams[i], dtype=np.uint8)[metas[i].audio_offset:], int(off[k]))
+        # tiles that do not overlap cover the window exactly when their clipped areas add up to it: only then is the
+        # zero fill (np.zeros in the host mosaic this replaces) skipped
+        covered = sum(max(0, min(w, c + tw) - max(0, c)) * max(0, min(h, r + th) - max(0, r)) for c, r, tw, th in wins)
+        if covered != h * w:
+            dst.upload(np.zeros((h, w), dtype=dtype))
+        k0 = 0
+        for (bps, bs), idx in groups.items():
+            k1 = k0 + len(idx)
+            ctx.decode_tiles_window_device(blob, off[k0:k1 + 1], [wins[i] for i in idx], bps,
+                                           [mds[i]["data_min"] for i in idx], [mds[i]["data_max"] for i in idx],
+                                           dtype, dst, (1, h, w), blocksize=bs)
+            k0 = k1
+    except BaseException:
+        dst.close()
+        raise
+    finally:
+        blob.close()
+    return dst, dtype
+
+
+def _download_raster(dst, dtype, h: int, w: int) -> np.ndarray:
+    out = np.empty((1, h, w), dtype=dtype)
+    try:
+        dst.download(out=out)
+    finally:
+        dst.close()
+    return out
+
+
 def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: Optional[Context] = None,
                         crop: bool = True):
-    """Extension: decode every tile intersecting bbox in one GPU batch and mosaic them into
-    the raster window they cover, cropped (crop=True) to the whole-pixel window of the bbox itself
-    (bbox_pixel_window).  Returns (array (1, h, w), window dict, transform list)."""
+    """Extension: decode every tile intersecting bbox in one GPU batch straight into the raster window
+    they cover, or (crop=True) into the whole-pixel window of the bbox itself (bbox_pixel_window): the tiles are
+    placed and clipped on the device (decode_into_window), the host only receives the final window.  Returns
+    (array (1, h, w), window dict, transform list)."""
     src = Source(flac_url)
     n, index = read_index(src)
     hits = intersecting(index, bbox)
     if not hits:
         raise LookupError(f"No tiles intersect with bbox {bbox}")
     datas = fetch_tiles(src, hits, n)
-    dec = TileDecoder(ctx).decode_streams(datas)
     c0 = min(f["window"]["col_off"] for f in hits)
     r0 = min(f["window"]["row_off"] for f in hits)
     c1 = max(f["window"]["col_off"] + f["window"]["width"] for f in hits)
     r1 = max(f["window"]["row_off"] + f["window"]["height"] for f in hits)
-    dtype = dec[0][0].dtype
-    out = np.zeros((1, r1 - r0, c1 - c0), dtype=dtype)
-    for f, (arr, _) in zip(hits, dec):
-        w = f["window"]
-        out[0, w["row_off"] - r0:w["row_off"] - r0 + w["height"], w["col_off"] - c0:w["col_off"] - c0 + w["width"]] = arr[0]
     t = geotiff.Affine(*index["transform"][:6])
     win = {"col_off": c0, "row_off": r0, "width": c1 - c0, "height": r1 - r0}
     if crop and t.b == 0 and t.d == 0:
@@ -537,7 +607,67 @@ def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: 
         a0, b0 = max(cw["col_off"], c0), max(cw["row_off"], r0)
         a1 = min(cw["col_off"] + cw["width"], c1)
         b1 = min(cw["row_off"] + cw["height"], r1)
-        out = np.ascontiguousarray(out[:, b0 - r0:max(b1, b0) - r0, a0 - c0:max(a1, a0) - c0])
         win = {"col_off": a0, "row_off": b0, "width": max(a1 - a0, 0), "height": max(b1 - b0, 0)}
+    if win["width"] == 0 or win["height"] == 0:  # an empty pixel window: nothing to decode
+        md = container.read_raster_tags(container.parse_metadata(datas[0]))
+        out = np.zeros((1, win["height"], win["width"]), dtype=np.dtype(md["dtype"]))
+    else:
+        dst, dtype = decode_into_window(datas, hits, (win["col_off"], win["row_off"]), (win["height"], win["width"]),
+                                        ctx)
+        out = _download_raster(dst, dtype, win["height"], win["width"])
     wt = geotiff.window_transform(t, win["col_off"], win["row_off"])
     return out, win, list(wt)
+
+
+def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None):
+    """Every tile of a streaming file in one batched decode, placed into the full raster in device memory.
+    Returns (DeviceBuffer, dtype, index)."""
+    src = Source(flac_url)
+    n, index = read_index(src)
+    frames = index["frames"]
+    if not frames:
+        raise ValueError("the streaming index lists no tiles")
+    datas = fetch_tiles(src, frames, n)
+    dst, dtype = decode_into_window(datas, frames, (0, 0), (int(index["height"]), int(index["width"])), ctx)
+    return dst, dtype, index
+
+
+def reconstruct(flac_url: Union[str, Path], ctx: Optional[Context] = None):
+    """The whole raster of a streaming file: (array (1, H, W), transform list)."""
+    dst, dtype, index = reconstruct_device(flac_url, ctx)
+    return _download_raster(dst, dtype, int(index["height"]), int(index["width"])), list(index["transform"])
+
+
+def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context] = None) -> Dict:
+    """extract-streaming --all: write the reconstruction as a GeoTIFF with the index's CRS and transform."""
+    arr, tr = reconstruct(flac_url, ctx)
+    _, index = read_index(flac_url)
+    crs = index.get("crs")
+    epsg = int(crs.split(":")[1]) if crs and str(crs).upper().startswith("EPSG:") else None
+    geotiff.write(Path(output), arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
+    return index
+
+
+def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optional[Context] = None) -> Dict:
+    """create-streaming --verify: read the written file back (what is checked is what is on disk), decode it into a
+    device raster through the window call, upload the source band and compare the two on the device
+    (frs_compare_device).  Returns the un-wrapped differences as compare's ``exact`` key: n_different,
+    max_difference, mean_difference, first_difference."""
+    from .compare import _exact
+    ctx = ctx or default_context()
+    band = np.asarray(band)
+    dst, dtype, index = reconstruct_device(flac_path, ctx)
+    try:
+        H, W = int(index["height"]), int(index["width"])
+        if band.shape != (H, W) or band.dtype != dtype:
+            raise ValueError(f"source band {band.shape} {band.dtype} does not match the file's {(H, W)} {dtype}")
+        srcbuf = ctx.alloc(band.nbytes)
+        try:
+            srcbuf.upload(band)
+            d = ctx.make_compare_desc(H, W, dtype)
+            bands = ctx.compare_device(srcbuf.ptr, dst.ptr, d)
+        finally:
+            srcbuf.close()
+    finally:
+        dst.close()
+    return _exact(bands, W)

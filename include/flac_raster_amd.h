@@ -202,6 +202,52 @@ int frs_compare_device(frs_ctx *ctx, const frs_compare_desc *desc, const void *a
 int frs_compare(frs_ctx *ctx, const frs_compare_desc *desc, const void *a_host, const void *b_host,
                 frs_compare_band *out_host);
 
+/* Place decoded tiles at their windows of a raster in device memory: the decoder-side mirror of frs_encode_desc's
+ * strided raster view.  Replaces streaming.extract_bbox_mosaic's host loop (np.zeros of the union window, one slice
+ * assignment per tile, a second copy for the crop) and converter.py's `.reshape(H, W, C).transpose(2, 0, 1)` +
+ * ascontiguousarray after a multi-band decode.
+ *   tiles_dev   what frs_decode_tiles_device writes: tile t is width*height pixels in row-major order, each pixel
+ *               nbands interleaved elements, starting at element pcm_off[t] * nbands (pcm_off: ntiles entries read)
+ *   win[t]      the tile's size and its position relative to the destination's origin; col_off / row_off may be
+ *               negative or reach past the destination's width / height
+ *   dst         [nbands][height][width] elements of `dtype` with the given strides (elements)
+ * Element (r, x) of channel c of tile t goes to
+ *   dst_dev + c*band_stride + (row_off[t] + r)*row_stride + (col_off[t] + x).
+ * Pixels outside the destination are dropped; a tile wholly outside writes nothing.  Destination elements that no tile
+ * covers are not touched, the row padding of row_stride > width included.  The windows of one call MUST NOT overlap
+ * inside the destination: this is not checked, and overlapping tiles race for the shared elements.  The kernel moves
+ * bytes only (every dtype by its element size; whole 16-byte chunks of a destination row by aligned 16-byte stores).
+ * FRS_E_ARG: ntiles < 0, a tile width or height < 1, a destination height or width < 1, row_stride < width, nbands
+ * outside 1..8, unknown dtype, a negative pcm_off, a null pointer or one not aligned to the element size; also a
+ * band_stride (nbands > 1) smaller than (height-1)*row_stride + width, an extent that overflows 63 bits, and a tile
+ * offset beyond +-2^61.  ntiles == 0 is FRS_OK without a launch.  Synchronous on the context stream.
+ *
+ * frs_decode_tiles_window_device = frs_decode_tiles_device + the placement: stream s is tile s, decoded (channels =
+ * dst->nbands, out_dtype = dst->dtype, samples win[s].width * win[s].height, pcm_off their prefix sums) into a
+ * staging buffer the context owns and grows, then placed.  Errors as frs_decode_tiles_device and as above; synchronous
+ * on return.  frs_decode_tiles_window takes a host blob and a host destination: the destination ((nbands-1)*band_stride
+ * + (height-1)*row_stride + width elements) is uploaded first and downloaded after the placement, so elements no tile
+ * covers survive the round trip. */
+typedef struct {
+    int64_t col_off, row_off;   /* position relative to the destination origin */
+    int32_t width, height;      /* tile size in pixels */
+} frs_tile_window;
+typedef struct {
+    int64_t height, width;      /* destination size in pixels */
+    int64_t row_stride;         /* elements between rows */
+    int64_t band_stride;        /* elements between bands */
+    int32_t dtype;              /* enum frs_dtype */
+    int32_t nbands;             /* 1..8: channels of every tile */
+} frs_raster_desc;
+int frs_place_tiles_device(frs_ctx *ctx, const frs_raster_desc *dst, const void *tiles_dev, const int64_t *pcm_off,
+                           const frs_tile_window *win, int32_t ntiles, void *dst_dev);
+int frs_decode_tiles_window_device(frs_ctx *ctx, const uint8_t *blob_dev, const int64_t *stream_off, int32_t nstreams,
+                                   int32_t bps, int32_t blocksize, const frs_tile_window *win, const double *data_min,
+                                   const double *data_max, const frs_raster_desc *dst, void *dst_dev);
+int frs_decode_tiles_window(frs_ctx *ctx, const uint8_t *blob_host, const int64_t *stream_off, int32_t nstreams,
+                            int32_t bps, int32_t blocksize, const frs_tile_window *win, const double *data_min,
+                            const double *data_max, const frs_raster_desc *dst, void *dst_host);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
@@ -241,7 +287,7 @@ int frs_synth_raster_device(frs_ctx *ctx, int16_t *dev, int32_t bands, int64_t h
 void *frs_ctx_stream(frs_ctx *ctx);
 /* Average device time (ms) of the named kernel over the launches since the last reset, measured with
  * HIP events on the context stream (kernel: "encode" = the frame-encode kernel, "analyze", "stats",
- * "compact", "decode", "compare"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
+ * "compact", "decode", "compare", "place"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
 int frs_profile_enable(frs_ctx *ctx, int on);
 double frs_profile_avg_ms(frs_ctx *ctx, const char *kernel);
 void frs_profile_reset(frs_ctx *ctx);
