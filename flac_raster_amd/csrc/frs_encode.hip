@@ -32,6 +32,7 @@
 
 #include "frs_internal.h"
 #include "frs_frame_header.h"
+#include "frs_crc16_fold.h"
 
 namespace frs {
 
@@ -1600,9 +1601,10 @@ __device__ inline uint32_t xpow8(uint64_t m) {  // x^(8m) mod P
 
 constexpr int kFrameWordsV3 = 2176;  // 69632 bits >= worst exact frame (estimate < verbatim)
 constexpr int kXpowBytes = kFrameWordsV3 * 4 + 64;  // multiple of 64 (LDS split tables)
-__constant__ uint16_t c_crc16x8[16][256];           // T_k[v] = CRC-16 of byte v followed by k zero bytes
+__constant__ uint16_t c_crc16x8[4][256];            // T_k[v] = CRC-16 of byte v followed by k zero bytes (slice-by-4)
 __device__ uint16_t g_xpow_bytes[kXpowBytes];      // x^(8m) mod P for m bytes
 __device__ uint16_t g_xpow_8k[32];                  // x^(8 * 8192 q) mod P
+__device__ uint16_t g_xpow_hi[(kXpowBytes + 63) / 64 + 3];  // x^(8 * 64 (j - 3)) mod P: k_encode_v4's column factors
 // x^(8m) mod P for a byte count m: one table read below kXpowBytes, two reads and a multiply below 256 KiB (frames
 // of up to 8 channels), the square-and-multiply loop beyond
 __device__ inline uint32_t xpow_bytes(int64_t m) {
@@ -2604,9 +2606,8 @@ constexpr int kSubWords = kFrameWordsV3 + 4;
 struct EncV3Shared {
     uint32_t bits[4][kBufWordsV3];
     int16_t lut[kLutCap];
-    uint16_t crc8x[16][256];  // slice-by-16 tables (T_0..T_3 serve the slice-by-4 / byte steps)
-    uint16_t xlo[64];       // x^(8m) mod P, m = 0..63
-    uint16_t xhi[kXpowHi];  // x^(8*64*m) mod P
+    uint16_t xlo[64];           // x^(8m) mod P, m = 0..63
+    uint16_t xhi[kXpowHi + 3];  // x^(8*64*(m - 3)) mod P (crc16_cols)
     uint8_t crc8[256];
     int ticket[2];
     int want[2];
@@ -3153,7 +3154,7 @@ __device__ __forceinline__ void rice_candidates(uint32_t sf, uint32_t sl, int of
 // write position at the end.  The frame is then assembled in place in a linear layout (word w at w): every lane
 // reads its column into registers, the buffer is zeroed, and the lane ORs its segment in at its bit offset (one
 // v_alignbit per word; words shared with a neighbour lane are OR-ed by both).  Header, warm-up and coefficient
-// fields are OR-ed at their fixed positions, the CRC-16 is summed per lane over word ranges, and only then does the
+// fields are OR-ed at their fixed positions, the CRC-16 is folded per lane over its column, and only then does the
 // wave look back for its frame's byte offset and store the frame (one buffer per wave: the store is not deferred to
 // the next frame, which leaves the assembly and CRC as the look-back's slack).  A lane whose segment outgrows its
 // column (> kPrivBits, e.g. a residual spike in an otherwise smooth frame) makes the whole wave repack from its
@@ -3173,46 +3174,25 @@ __device__ inline void zero_wave_buf(uint32_t *buf, int lane) {
     }
 }
 
-// CRC-16 of body bytes [0, body) of a frame in the column layout M: lane L takes column L (words L C .. L C + C - 1,
-// so at each step the lanes read one row: consecutive banks) by slice-by-16, the lane holding the last whole word adds
-// the tail bytes, and the lanes' values are combined with x^(8m) factors (m = bytes after the lane's range)
+// CRC-16 of body bytes [0, body) of a frame in the column layout M, without a table (frs_crc16_fold.h).  Lane L takes
+// column L as a message of kCrcRows words: its C rows (at each step the lanes read one row: consecutive banks) and
+// kCrcRows - C zero words that are never read, so a word's place in the fold is fixed when the kernel is compiled.
+// The buffer is zero past the body (it is zeroed before the assembly, and every field is OR-ed in at its exact width),
+// so the columns are read whole: the tail bytes and the lanes past the frame's end need no case of their own.  The
+// lanes' values are combined with x^(8m) factors, m = body - 4 C L - 4 kCrcRows bytes after the lane's message; m is
+// negative (above -4 kCrcRows) in the lane that holds the frame's end, so the table index is biased by kCrcBias and
+// xhi begins with three negative powers (x has an inverse mod P).  A lane past the end holds zeros: its CRC is 0
+// whatever the factor, and its index is clamped.
+constexpr int kCrcRows = kFrameWordsV3 / 64;  // rows a frame's layout can have (fb_map: C <= 34)
+constexpr int kCrcBias = 192;                 // bytes; a multiple of 64 above 4 kCrcRows
+static_assert(kFrameWordsV3 % 64 == 0 && kCrcRows <= frs::kCrcFoldSpan && kCrcBias % 64 == 0 && kCrcBias >= 4 * kCrcRows,
+              "column CRC");
+static_assert(kCrcRows * 64 <= kBufWordsV3 && sizeof(g_xpow_hi) == sizeof(uint16_t) * (kXpowHi + 3),
+              "the rows read (in groups of 8, below kCrcRows) are the buffer's; the factor table");
 __device__ __forceinline__ uint32_t crc16_cols(const uint32_t *fbuf, const FbMap &M, uint32_t body, const EncV3Shared &S,
                                                int lane) {
-    const uint32_t nfw = body >> 2, tail = body & 3;
-    const uint32_t wb = min(nfw, (uint32_t)lane * M.c), we = min(nfw, wb + M.c);
-    uint32_t c = 0;
-    const uint32_t *colp = fbuf + lane;
-    const uint16_t(*T)[256] = S.crc8x;
-    uint32_t i = wb;
-    for (; i + 3 < we; i += 4, colp += 256) {
-        const uint32_t w0 = colp[0], w1 = colp[64], w2 = colp[128], w3 = colp[192];
-        c = (uint32_t)T[15][((c >> 8) ^ (w0 >> 24)) & 0xFF] ^ T[14][((c & 0xFF) ^ (w0 >> 16)) & 0xFF] ^
-            T[13][(w0 >> 8) & 0xFF] ^ T[12][w0 & 0xFF] ^ T[11][w1 >> 24] ^ T[10][(w1 >> 16) & 0xFF] ^
-            T[9][(w1 >> 8) & 0xFF] ^ T[8][w1 & 0xFF] ^ T[7][w2 >> 24] ^ T[6][(w2 >> 16) & 0xFF] ^
-            T[5][(w2 >> 8) & 0xFF] ^ T[4][w2 & 0xFF] ^ T[3][w3 >> 24] ^ T[2][(w3 >> 16) & 0xFF] ^
-            T[1][(w3 >> 8) & 0xFF] ^ T[0][w3 & 0xFF];
-    }
-    for (; i + 1 < we; i += 2, colp += 128) {
-        const uint32_t w0 = colp[0], w1 = colp[64];
-        c = (uint32_t)T[7][((c >> 8) ^ (w0 >> 24)) & 0xFF] ^ T[6][((c & 0xFF) ^ (w0 >> 16)) & 0xFF] ^
-            T[5][(w0 >> 8) & 0xFF] ^ T[4][w0 & 0xFF] ^ T[3][w1 >> 24] ^ T[2][(w1 >> 16) & 0xFF] ^
-            T[1][(w1 >> 8) & 0xFF] ^ T[0][w1 & 0xFF];
-    }
-    if (i < we) {
-        const uint32_t word = *colp;
-        c = (uint32_t)T[3][((c >> 8) ^ (word >> 24)) & 0xFF] ^ T[2][((c & 0xFF) ^ (word >> 16)) & 0xFF] ^
-            T[1][(word >> 8) & 0xFF] ^ T[0][word & 0xFF];
-    }
-    uint32_t end = we * 4;
-    if (lane == (int)M.col(nfw - 1)) {
-        const uint32_t word = fbuf[M(nfw)];
-        for (uint32_t b = 0; b < tail; b++) {
-            const uint32_t byte = (word >> (24 - 8 * b)) & 0xFF;
-            c = ((c << 8) & 0xFFFFu) ^ S.crc8x[0][((c >> 8) ^ byte) & 0xFF];
-        }
-        end += tail;
-    }
-    const uint32_t m = body - end;
+    const uint32_t c = frs::crc16_column<kCrcRows, 8>(fbuf + lane, 64, (int)M.c);
+    const int m = max(0, (int)body + (kCrcBias - 4 * kCrcRows) - 4 * (int)M.c * lane);
     return dpp_wave_xor_u32(gf_mulmod(gf_mulmod(c, S.xlo[m & 63]), S.xhi[m >> 6]));
 }
 
@@ -3715,8 +3695,8 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
 // pass (ST): left, right, mid in one launch, the 17-bit side signals (WIDE) in another.
 template <int DT, bool SUB = false, bool ST = false, bool WIDE = false>
 // (3 waves per SIMD for mono / >= 3-channel 16-bit units; 2 for the two-channel launches: convert_2band encode
-// 3.17 -> 2.78 ms against 1 wave per SIMD.  With the frame state scalar the mono instance takes 140 VGPRs of its 168
-// and L/R/M 157; the int32 side, in its vector form, 255 without a spill)
+// 3.17 -> 2.78 ms against 1 wave per SIMD.  With the frame state scalar the mono instance takes 144 VGPRs of its 168
+// and L/R/M 159; the int32 side, in its vector form, 256 without a spill)
 __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ? 2 : 3) : 1) k_encode_v4(const typename Elem<DT>::T *raster, EncodeParams P,
                                                   const TileGeom *__restrict__ tiles,
                                                   const TileNorm *__restrict__ norms, const int16_t *__restrict__ luts,
@@ -3738,10 +3718,9 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
     constexpr bool kUni = !WIDE;
     // (uni: the launch is 1-D with 256 threads, so the 64 threads of a wave share threadIdx.x >> 6)
     const int wave = (int)uni_if<kUni>(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    for (int i = threadIdx.x; i < 4096; i += blockDim.x) (&S.crc8x[0][0])[i] = (&c_crc16x8[0][0])[i];
     for (int i = threadIdx.x; i < 256; i += blockDim.x) S.crc8[i] = c_crc8[i];
     for (int i = threadIdx.x; i < 64; i += blockDim.x) S.xlo[i] = g_xpow_bytes[i];
-    for (int i = threadIdx.x; i < kXpowHi; i += blockDim.x) S.xhi[i] = g_xpow_bytes[64 * i];
+    for (int i = threadIdx.x; i < kXpowHi + 3; i += blockDim.x) S.xhi[i] = g_xpow_hi[i];
     for (int i = threadIdx.x; i < 4 * kBufWordsV3; i += blockDim.x) (&S.bits[0][0])[i] = 0;
     if (threadIdx.x == 0) S.lut_tile = -1;
     PendingFrame prev;
@@ -4035,11 +4014,11 @@ static int upload_tables(frs_ctx *ctx) {
     FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_crc8), t8, 256, 0, hipMemcpyHostToDevice, ctx->stream));
     FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_crc16), t16, sizeof(t16), 0, hipMemcpyHostToDevice, ctx->stream));
     FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_xpow8), xp, sizeof(xp), 0, hipMemcpyHostToDevice, ctx->stream));
-    // slice-by-16 tables: T_k[v] = T_{k-1}[v] advanced by one zero byte
-    static uint16_t t4[16][256];
+    // slice-by-4 tables: T_k[v] = T_{k-1}[v] advanced by one zero byte
+    static uint16_t t4[4][256];
     static uint16_t xb[kXpowBytes];
     for (int i = 0; i < 256; i++) t4[0][i] = t16[i];
-    for (int k = 1; k < 16; k++)
+    for (int k = 1; k < 4; k++)
         for (int i = 0; i < 256; i++) {
             const uint16_t c = t4[k - 1][i];
             t4[k][i] = (uint16_t)(((c << 8) & 0xFFFF) ^ t16[c >> 8]);
@@ -4060,6 +4039,9 @@ static int upload_tables(frs_ctx *ctx) {
         q = mulmod(q, x8192);
     }
     FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xpow_8k), x8k, sizeof(x8k), 0, hipMemcpyHostToDevice, ctx->stream));
+    static uint16_t xhi[kXpowHi + 3];
+    for (int j = 0; j < kXpowHi + 3; j++) xhi[j] = (uint16_t)frs::crc16_xpow(512L * (j - 3));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xpow_hi), xhi, sizeof(xhi), 0, hipMemcpyHostToDevice, ctx->stream));
     FRS_HIP(hipStreamSynchronize(ctx->stream));
     g_tables_ready[ctx->device] = true;
     return FRS_OK;

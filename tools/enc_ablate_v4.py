@@ -70,43 +70,8 @@ T8 = chain(
                 encode_frame_v4<DT>(raster, P, tiles, norms, ana, arena, arena_cap, frame_off, status, err, S, want, f,
                                     lane, ftile, prev, hdr_tab, hdr_n, pslots, pbytes, 0, nullptr, nullptr, dbg);
             }"""))
-# the frame CRC in two interleaved chains per lane (halves of its column), joined with one x^(8m) factor
-CRC2 = gsub("""    uint32_t c = 0;
-    const uint32_t *colp = fbuf + lane;
-    const uint16_t(*T)[256] = S.crc8x;
-    uint32_t i = wb;
-    for (; i + 3 < we; i += 4, colp += 256) {""", """    uint32_t c = 0;
-    const uint32_t *colp = fbuf + lane;
-    const uint16_t(*T)[256] = S.crc8x;
-    uint32_t i = wb;
-    const uint32_t nst = (we - wb) >> 3;  // 4-word steps of each chain
-    if (nst) {
-        uint32_t ca = 0, cb = 0;
-        const uint32_t *pa = colp, *pb = colp + 256 * nst;
-        for (uint32_t st = 0; st < nst; st++, pa += 256, pb += 256) {
-            const uint32_t w0 = pa[0], w1 = pa[64], w2 = pa[128], w3 = pa[192];
-            const uint32_t x0 = pb[0], x1 = pb[64], x2 = pb[128], x3 = pb[192];
-            ca = (uint32_t)T[15][((ca >> 8) ^ (w0 >> 24)) & 0xFF] ^ T[14][((ca & 0xFF) ^ (w0 >> 16)) & 0xFF] ^
-                T[13][(w0 >> 8) & 0xFF] ^ T[12][w0 & 0xFF] ^ T[11][w1 >> 24] ^ T[10][(w1 >> 16) & 0xFF] ^
-                T[9][(w1 >> 8) & 0xFF] ^ T[8][w1 & 0xFF] ^ T[7][w2 >> 24] ^ T[6][(w2 >> 16) & 0xFF] ^
-                T[5][(w2 >> 8) & 0xFF] ^ T[4][w2 & 0xFF] ^ T[3][w3 >> 24] ^ T[2][(w3 >> 16) & 0xFF] ^
-                T[1][(w3 >> 8) & 0xFF] ^ T[0][w3 & 0xFF];
-            cb = (uint32_t)T[15][((cb >> 8) ^ (x0 >> 24)) & 0xFF] ^ T[14][((cb & 0xFF) ^ (x0 >> 16)) & 0xFF] ^
-                T[13][(x0 >> 8) & 0xFF] ^ T[12][x0 & 0xFF] ^ T[11][x1 >> 24] ^ T[10][(x1 >> 16) & 0xFF] ^
-                T[9][(x1 >> 8) & 0xFF] ^ T[8][x1 & 0xFF] ^ T[7][x2 >> 24] ^ T[6][(x2 >> 16) & 0xFF] ^
-                T[5][(x2 >> 8) & 0xFF] ^ T[4][x2 & 0xFF] ^ T[3][x3 >> 24] ^ T[2][(x3 >> 16) & 0xFF] ^
-                T[1][(x3 >> 8) & 0xFF] ^ T[0][x3 & 0xFF];
-        }
-        const uint32_t mb = 16 * nst;  // chain b's bytes: ca advanced past them
-        c = gf_mulmod(gf_mulmod(ca, S.xlo[mb & 63]), S.xhi[mb >> 6]) ^ cb;
-        i = wb + 8 * nst;
-        colp += 512 * nst;
-    }
-    for (; i + 3 < we; i += 4, colp += 256) {""")
-
 VARIANTS = {
     "v4t8": T8,
-    "v4crc2": CRC2,
     "v4earlypub": EARLYPUB,
     "v4base": lambda s: s,
     "v4noasm": NOASM,
