@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "frs_normalize.h"
+
 namespace frs {
 
 constexpr int kMaxLpc = 8;
@@ -36,11 +38,7 @@ struct TileNorm {
     int32_t has_range;   // max > min
     int32_t mode;        // kNorm*: how the fast kernels normalise this tile
 };
-constexpr int kNormLut = 0;      // pcm = lut[x - min] (R + 1 <= kLutCap entries, built once per tile)
-constexpr int kNormFastDiv = 1;  // no wrap, den <= 65535: RN(2d/den) by reciprocal + 2 FMA (exhaustively exact)
-constexpr int kNormSlow = 2;     // anything else (wrapping int16, 32-bit dtypes, floats): IEEE division
-constexpr int kNormZero = 3;     // max == min: zeros
-constexpr int kLutCap = 4096;    // LUT entries per tile
+// (the modes kNorm* and kLutCap: frs_normalize.h)
 
 // Per-subframe decision inputs produced by the analysis kernel (lane = subframe).
 struct SubAnalysis {
@@ -110,12 +108,7 @@ struct LpcCand {
 __host__ __device__ inline int ilog2_u32(uint32_t v) { return 31 - __builtin_clz(v); }
 __host__ __device__ inline int ilog2_u64(uint64_t v) { return 63 - __builtin_clzll(v); }
 
-// numpy's float64 -> int32 cast as compiled on x86-64 (cvttsd2si): truncation, out of range or NaN
-// gives INT32_MIN ("integer indefinite").  The gfx950 v_cvt_i32_f64 saturates instead, so guard it.
-__device__ inline int32_t cast_f64_i32_x86(double v) {
-    if (!(v > -2147483649.0 && v < 2147483648.0)) return INT32_MIN;
-    return (int32_t)v;
-}
+// (cast_f64_i32_x86, numpy's float64 -> int32 cast on x86-64: frs_normalize.h)
 
 // libm-compatible lround (half away from zero) without the floor(x+0.5) double rounding trap.
 __device__ inline int64_t lround_exact(double e) {

@@ -96,10 +96,8 @@ template <int DT> struct Normalizer {
             if (!has_range) return 0;
             T d = (T)((int64_t)x - (int64_t)mn);
             double v;
-            if (fastdiv) {  // RN(2d / den) by reciprocal + two FMAs: exhaustively exact for d <= den <= 65535
-                const double a = 2.0 * (double)d;
-                const double q0 = a * rinv;
-                v = fma(fma(-q0, den, a), rinv, q0) - 1.0;
+            if (fastdiv) {  // RN(2d / den) by reciprocal + two FMAs, d <= den <= 65535: tests/test_normalize_host.py
+                v = norm_quot_recip(2.0 * (double)d, den, rinv) - 1.0;
             } else {
                 v = (2.0 * (double)d) / den - 1.0;
             }
@@ -269,6 +267,10 @@ template <int DT> __device__ inline void tile_norm_finalize(TileNorm &n, int nor
         n.dmax = (double)n.imax;
         n.has_range = n.imax > n.imin;
         n.den = (double)(T)(n.imax - n.imin);  // data_max - data_min in the dtype (wraps for int16)
+        // The mode choice below is a COPY of frs_normalize.h's norm_mode_of(imin, imax, bits and signedness of T,
+        // norm_mode, scale_bits), which tests/test_normalize_host.py checks at every cut-off: calling it here changed
+        // the code of k_tile_finalize and of the k_analyze_v3<..., STATS> instances (same registers, the range test
+        // compiled another way), so the text stays as it was.  Change both together.
         const int64_t R = n.imax - n.imin;
         const bool nowrap = (int64_t)(T)R == R;  // x - min and max - min never wrap in the dtype
         if (norm_mode == 0 && scale_bits == 16) {
@@ -1748,19 +1750,12 @@ __device__ inline int32_t norm_fast(typename Elem<DT>::T x, const TileNorm &tn, 
         switch (tn.mode) {
         case kNormLut: return lut[d];
         case kNormZero: return 0;
-        case kNormFastDiv: {
-            const double a = (double)(2 * d);
-            const double q0 = a * tn.rinv;
-            const double r = fma(-q0, tn.den, a);
-            const double q1 = fma(r, tn.rinv, q0);  // == RN(a / den): verified for every d <= den <= 65535
-            const double v = (q1 - 1.0) * 32767.0;
-            return (int32_t)(int16_t)cast_f64_i32_x86(v);
-        }
+        case kNormFastDiv:  // == RN(2d / den): tests/test_normalize_host.py, every d <= den <= 65535
+            return norm16_recip((double)(2 * d), tn.den, tn.rinv);
         default: {
             using T = typename Elem<DT>::T;
             const T dd = (T)((int64_t)x - tn.imin);
-            const double v = ((2.0 * (double)dd) / tn.den - 1.0) * 32767.0;
-            return (int32_t)(int16_t)cast_f64_i32_x86(v);
+            return norm16_div((double)dd, tn.den);
         }
         }
     }
@@ -1791,11 +1786,7 @@ __device__ inline void norm_chunk(const Chunk64<DT> &ch, const TileNorm &tn, con
         const double rinv = tn.rinv, den = tn.den;
 #pragma unroll
         for (int j = 0; j < 64; j++) {
-            const double a = (double)(2 * ((int32_t)ch.get(j) - mn));
-            const double q0 = a * rinv;
-            const double r = fma(-q0, den, a);
-            const double q1 = fma(r, rinv, q0);
-            emit(j, (int32_t)(int16_t)(int32_t)((q1 - 1.0) * 32767.0));
+            emit(j, norm16_recip_inrange((double)(2 * ((int32_t)ch.get(j) - mn)), den, rinv));
         }
         break;
     }
@@ -1804,7 +1795,7 @@ __device__ inline void norm_chunk(const Chunk64<DT> &ch, const TileNorm &tn, con
         for (int j = 0; j < 64; j++) {
             using T = typename Elem<DT>::T;
             const T dd = (T)((int64_t)ch.get(j) - tn.imin);
-            emit(j, (int32_t)(int16_t)cast_f64_i32_x86(((2.0 * (double)dd) / tn.den - 1.0) * 32767.0));
+            emit(j, norm16_div((double)dd, tn.den));
         }
         break;
     }
@@ -1814,8 +1805,7 @@ __device__ inline void norm_chunk(const Chunk64<DT> &ch, const TileNorm &tn, con
 template <int DT> __device__ inline int16_t lut_entry(const TileNorm &tn, int64_t d) {
     using T = typename Elem<DT>::T;
     const T dd = (T)d;
-    const double v = ((2.0 * (double)dd) / tn.den - 1.0) * 32767.0;
-    return (int16_t)cast_f64_i32_x86(v);
+    return (int16_t)norm16_div((double)dd, tn.den);
 }
 
 template <int DT>
@@ -1827,13 +1817,7 @@ __global__ void __launch_bounds__(256) k_build_lut(const TileNorm *norms, int16_
     for (int64_t d = threadIdx.x; d <= R; d += blockDim.x) luts[(int64_t)t * kLutCap + d] = lut_entry<DT>(tn, d);
 }
 
-// n / d for n < 2^32 via a double reciprocal (inv = 1.0 / d): the estimate is off by at most one, fixed up
-__device__ inline uint32_t udiv_inv(uint32_t n, uint32_t d, double inv) {
-    uint32_t q = (uint32_t)((double)n * inv);
-    const int64_t r = (int64_t)n - (int64_t)q * d;
-    q = r < 0 ? q - 1 : (r >= (int64_t)d ? q + 1 : q);
-    return q;
-}
+// (udiv_inv, n / d via a double reciprocal: frs_normalize.h)
 
 // N (32 or 64) consecutive elements of a frame, kept packed in 32-bit words (int16, N = 64: 32 words).
 // vec: 16-byte loads of one row segment; otherwise an element gather with a row cursor.
@@ -2209,11 +2193,7 @@ __device__ inline int32_t ana_norm(typename Elem<DT>::T x, const TileNorm &tn, c
     } else if constexpr (KIND == kAnaKindZero) {
         return 0;
     } else if constexpr (KIND == kAnaKindFastDiv) {
-        const double a = (double)(2 * ((int32_t)x - (int32_t)tn.imin));
-        const double q0 = a * tn.rinv;
-        const double r = fma(-q0, tn.den, a);
-        const double q1 = fma(r, tn.rinv, q0);
-        return (int32_t)(int16_t)(int32_t)((q1 - 1.0) * 32767.0);
+        return norm16_recip_inrange((double)(2 * ((int32_t)x - (int32_t)tn.imin)), tn.den, tn.rinv);
     } else {
         return norm_fast<DT>(x, tn, glut);
     }
