@@ -4,15 +4,35 @@
 // FLAC__stream_decoder_process_until_end_of_stream, docs/sonos-pyflac.txt:1584-1640, 1809-1854) and
 // converter.py:88-110 (_denormalize_from_audio), as used by cli.py:1022-1023 (extract-streaming).
 //
-// Frames carry no size field and STREAMINFO min/max framesize are 0 in these files, so frames are
-// located in parallel: k_sync_select finds every byte that starts a sync code with a parseable,
-// CRC-8-correct header and compacts them, in one pass (block counts + decoupled look-back), into the
-// sorted candidate list (bounded: overflow is counted, never written); k_span_crc_wave finds for each
-// candidate the first later candidate (or stream end) whose preceding two bytes are the CRC-16 of the
-// span; k_chain_lds follows those spans from each stream's first byte (so false syncs inside frame data
-// are never used); the frame decoders decode the true frames and check that the subframes end exactly at
-// the CRC footer.  Positions are 64-bit throughout (a C4 arena is 3.1 GB); candidate indices are int32
-// and the candidate buffer is capped below 2^31.
+// Frames carry no size field and STREAMINFO min/max framesize are 0 in these files, so frames are located in
+// parallel.  Positions are 64-bit throughout (a C4 arena is 3.1 GB); candidate indices are int32 and the candidate
+// buffer is capped below 2^31.  The device code comes first, by stage; the host code at the end (decode_job) plans
+// a call (plan_decode_route, frs_decode_plan.h) and runs the stages:
+//
+//   selection    every byte that starts a sync code with a parseable, CRC-8-correct header (header_ok_regs /
+//                parse_header, frs_frame_header.h), compacted into the sorted candidate list (bounded: overflow is
+//                counted, never written)
+//                one-pass  k_sync_select<4> / <16>: block counts + decoupled look-back (ranges up to 16 MB)
+//                two-pass  k_sync_count -> k_sync_scan -> k_sync_scatter (a whole arena)
+//   prefix CRC   the two-pass selection folds the CRC-16 of the bytes it reads (k_bound_mark, k_sync_count<true>,
+//                k_sync_scan, k_sync_scatter<true>) when the span check takes it from there
+//   span check   for each candidate the first later candidate (or stream end) whose preceding two bytes are the
+//                CRC-16 of the span:
+//                k_span_crc_wave   one wave per candidate (the pipelined decoder's small ranges)
+//                k_span_crc_lane   one lane per candidate (batched mono; long multi-channel / 32-bit frames)
+//                k_span_pcrc       one comparison per candidate pair, from the prefix CRCs
+//   chain        k_chain_lds follows those spans from each stream's first byte (so false syncs inside frame data
+//                are never used)
+//   frame decoders  decode the true frames and check that the subframes end exactly at the CRC footer:
+//                k_decode_frames_pipe          mono, few frames (a C5 query): producer / consumer waves per frame;
+//                                              <true> is the optimistic form, launched right after the selection
+//                                              with no span check and no chain, which may decline
+//                k_decode_frames_lane          mono, many frames: a lane per frame
+//                k_decode_frames_lane<.., true> + k_interleave_dn   2..8 channels: the lane walk into a planar
+//                                              scratch, then interleave (and de-normalise)
+//                k_decode_frames_wave          the rest (32-bit, > 8 channels, long blocks): a wave per frame
+//   fallback list   frames the lane decoders decline go through k_decode_frames_wave_list
+//   k_denormalize   the unfused de-normalisation (denormalize_job)
 #include <stdlib.h>
 #include <string.h>
 
@@ -23,49 +43,38 @@
 #include <vector>
 
 #include "frs_internal.h"
+#include "frs_frame_header.h"
+#include "frs_crc16_fold.h"
+#include "frs_decode_plan.h"
 
 namespace frs {
 
 __constant__ uint8_t d_crc8[256];
 __constant__ uint16_t d_crc16[256];
 __device__ __attribute__((aligned(16))) uint16_t d_crc16x4[4][256];  // slice-by-4 tables (T_0 = d_crc16), host-computed once per device
-__device__ __attribute__((aligned(16))) uint16_t d_xpow_lo[256];   // x^(8m) mod P, m < 256
-__device__ uint16_t d_xpow_hi[4096];  // x^(8*256*m) mod P
+__device__ __attribute__((aligned(16))) uint16_t d_xpow_lo[kDecXpowLo];   // x^(8m) mod P, m < 256
+__device__ uint16_t d_xpow_hi[kDecXpowHi];  // x^(8*256*m) mod P
 
-// a * b mod P (CRC-16 polynomial P = x^16 + x^15 + x^2 + 1), bitwise
-__device__ inline uint32_t dec_gfmul(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 15; i >= 0; i--) {
-        r <<= 1;
-        if (r & 0x10000u) r ^= 0x18005u;
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-// c * x^(8m) mod P: the CRC state c advanced over m zero bytes (m < 2^20)
+// c * x^(8m) mod P (the CRC-16 polynomial): the CRC state c advanced over m zero bytes (m < kDecXpowRange)
 __device__ inline uint32_t crc_xpow(uint32_t c, uint32_t m) {
     if (c == 0 || m == 0) return c;
-    return dec_gfmul(dec_gfmul(c, d_xpow_lo[m & 255]), d_xpow_hi[m >> 8]);
+    return crc16_mulmod(crc16_mulmod(c, d_xpow_lo[m & 255]), d_xpow_hi[m >> 8]);
 }
 __device__ inline uint32_t gf_pow16(uint32_t b, uint64_t e) {  // b^e mod P
     uint32_t r = 1;
     while (e) {
-        if (e & 1) r = dec_gfmul(r, b);
-        b = dec_gfmul(b, b);
+        if (e & 1) r = crc16_mulmod(r, b);
+        b = crc16_mulmod(b, b);
         e >>= 1;
     }
     return r;
 }
 
-struct FrameHdr {
-    int32_t ok;
-    int32_t frame_no;  // frame number from the header
-    int32_t bs;        // block size
-    int32_t hdr_len;   // header bytes incl. CRC-8
-    int32_t chass;     // channel assignment
-    int32_t bps;       // sample size
-};
+// parse_header (frs_frame_header.h) with the device's CRC-8 table: the one device function the selection's fallback
+// and the frame decoders call
+__device__ FrameHdr parse_header(const uint8_t *blob, int64_t p, int64_t end, int channels, int stream_bps) {
+    return parse_header(blob, p, end, channels, stream_bps, d_crc8);
+}
 
 __device__ inline int stream_of(const int64_t *soff, int ns, int64_t p) {
     int lo = 0, hi = ns - 1;
@@ -77,55 +86,6 @@ __device__ inline int stream_of(const int64_t *soff, int ns, int64_t p) {
     return lo;
 }
 
-// Parse + CRC-8-check a frame header at p (RFC 9639 9.1); end = end of the containing stream.
-__device__ FrameHdr parse_header(const uint8_t *blob, int64_t p, int64_t end, int channels, int stream_bps) {
-    FrameHdr h;
-    h.ok = 0;
-    if (p + 6 > end) return h;
-    if (blob[p] != 0xFF || (blob[p + 1] & 0xFE) != 0xF8) return h;
-    const uint8_t b2 = blob[p + 2], b3 = blob[p + 3];
-    const int bsc = b2 >> 4, src = b2 & 15, chass = b3 >> 4, ssc = (b3 >> 1) & 7;
-    if (bsc == 0 || src == 15 || chass > 10 || ssc == 3 || (b3 & 1)) return h;
-    int64_t q = p + 4;
-    uint32_t v = blob[q++];
-    int extra = 0;
-    if (v & 0x80) {
-        if ((v & 0xE0) == 0xC0) { extra = 1; v &= 0x1F; }
-        else if ((v & 0xF0) == 0xE0) { extra = 2; v &= 0x0F; }
-        else if ((v & 0xF8) == 0xF0) { extra = 3; v &= 0x07; }
-        else if ((v & 0xFC) == 0xF8) { extra = 4; v &= 0x03; }
-        else if ((v & 0xFE) == 0xFC) { extra = 5; v &= 0x01; }
-        else return h;
-    }
-    for (int i = 0; i < extra; i++) {
-        if (q >= end) return h;
-        const uint8_t c = blob[q++];
-        if ((c & 0xC0) != 0x80) return h;
-        v = (v << 6) | (c & 0x3F);
-    }
-    int bs;
-    if (bsc == 1) bs = 192;
-    else if (bsc >= 2 && bsc <= 5) bs = 576 << (bsc - 2);
-    else if (bsc == 6) { if (q >= end) return h; bs = blob[q++] + 1; }
-    else if (bsc == 7) { if (q + 1 >= end) return h; bs = ((blob[q] << 8) | blob[q + 1]) + 1; q += 2; }
-    else bs = 256 << (bsc - 8);
-    if (src == 12) q += 1;
-    else if (src == 13 || src == 14) q += 2;
-    if (q >= end) return h;
-    uint8_t c = 0;
-    for (int64_t i = p; i < q; i++) c = d_crc8[c ^ blob[i]];
-    if (c != blob[q]) return h;
-    const int nch = chass < 8 ? chass + 1 : 2;
-    if (nch != channels) return h;
-    h.ok = 1;
-    h.frame_no = (int32_t)v;
-    h.bs = bs;
-    h.hdr_len = (int32_t)(q + 1 - p);
-    h.chass = chass;
-    h.bps = ssc == 1 ? 8 : ssc == 2 ? 12 : ssc == 4 ? 16 : ssc == 5 ? 20 : ssc == 6 ? 24 : ssc == 7 ? 32 : stream_bps;
-    return h;
-}
-
 // ---------------------------------------------------------------------------------- candidate selection
 // One pass over the blob: a block takes 64 KB (16 KB per wave, coalesced 16-byte loads: sel_masks_co), flags the bytes that
 // start a sync code with a parseable CRC-8-correct header, and writes their positions, in order, at its
@@ -133,77 +93,12 @@ __device__ FrameHdr parse_header(const uint8_t *blob, int64_t p, int64_t end, in
 // (one wave).  Blocks take their ordinal from a ticket (the block that draws the last ticket re-arms the counter
 // for the next call), so a predecessor is always resident or done.  Status word: [63:40] call epoch, [39:38]
 // flag, [37:0] count; words of another epoch read as "not published", so the buffer is never cleared.
-constexpr int kSelThreads = 256, kSelBytes = 64 * 1024;  // 4 waves x 16 KB per block
 constexpr uint64_t kSelAgg = 1ull << 38, kSelIncl = 2ull << 38, kSelVal = (1ull << 38) - 1;
 
 __device__ inline int64_t wave_sum_i64(int64_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// Coalesced candidate flags: wave w of a 64 KB block takes the contiguous 16 KB at qw = block base + 16 KB w; step k
-// of it is the 1 KB at qw + 1024 k, lane L its 16 bytes at + 16 L (one fully coalesced 16-byte load per lane and
-// step), and the byte after them comes from lane L + 1 (lane 63: the next step's lane 0, or one guarded byte after
-// the last step).  Bit j of m[k] marks a sync code with a parseable, CRC-8-correct header at qw + 1024 k + 16 L + j,
-// so candidates are ordered by (k, lane, j).  Returns the lane's candidate count.
-constexpr int kSelSteps = kSelBytes / (kSelThreads / 64) / 1024;  // 16 steps of 1 KB per wave
-static_assert(kSelSteps == 16, "64 KB blocks of 4 waves");
-// small ranges (a C5 query's tile, <= 4 MB): 16 KB blocks of 4 waves x 4 steps, so a 0.5 MB tile spreads over 32
-// work-groups instead of 8 (the one-pass selection is latency-bound there)
-constexpr int kSelStepsSmall = 4;
-
-// CRC-8 (poly 0x07) of one byte folded into c, bitwise (no table: the header check runs from registers)
-__device__ inline uint32_t crc8_byte(uint32_t c, uint32_t b) {
-    c ^= b;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c = (c & 0x80u) ? ((c << 1) ^ 0x07u) & 0xFFu : (c << 1) & 0xFFu;
-    return c;
-}
-
-// parse_header on the 16 bytes h (little-endian dwords) that start at a sync code, `avail` bytes of the blob from
-// there: the same acceptance test (RFC 9639 9.1: reserved codes, UTF-8 frame number, CRC-8, channel count).
-__device__ inline bool header_ok_regs(const uint32_t *h, int64_t avail, int channels) {
-    auto B = [&](int t) -> uint32_t { return (h[t >> 2] >> (8 * (t & 3))) & 0xFFu; };
-    if (avail < 6) return false;
-    const uint32_t b2 = B(2), b3 = B(3);
-    const uint32_t bsc = b2 >> 4, src = b2 & 15, chass = b3 >> 4, ssc = (b3 >> 1) & 7;
-    if (bsc == 0 || src == 15 || chass > 10 || ssc == 3 || (b3 & 1)) return false;
-    const uint32_t v = B(4);
-    int extra = 0;
-    if (v & 0x80) {
-        if ((v & 0xE0) == 0xC0) extra = 1;
-        else if ((v & 0xF0) == 0xE0) extra = 2;
-        else if ((v & 0xF8) == 0xF0) extra = 3;
-        else if ((v & 0xFC) == 0xF8) extra = 4;
-        else if ((v & 0xFE) == 0xFC) extra = 5;
-        else return false;
-    }
-    int q = 5;
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        if (i < extra) {
-            if (q >= avail || (B(5 + i) & 0xC0) != 0x80) return false;
-            q++;
-        }
-    }
-    if (bsc == 6) {
-        if (q >= avail) return false;
-        q += 1;
-    } else if (bsc == 7) {
-        if (q + 1 >= avail) return false;
-        q += 2;
-    }
-    if (src == 12) q += 1;
-    else if (src == 13 || src == 14) q += 2;
-    if (q >= avail) return false;  // q <= 14: the CRC-8 byte is h's byte q
-    uint32_t c = 0;
-#pragma unroll
-    for (int t = 0; t < 15; t++)
-        if (t < q) c = crc8_byte(c, B(t));
-    if (c != B(q)) return false;
-    const int nch = chass < 8 ? (int)chass + 1 : 2;
-    return nch == channels;
 }
 
 // dword idx (0..7) of the 32-byte window w0 | w1, idx dynamic (a select chain, no register indexing)
@@ -716,11 +611,11 @@ __global__ void __launch_bounds__(kSelThreads) k_sync_select(const uint8_t *blob
         if (ord == 0) {
             if (lane == 0) {
                 __hip_atomic_store(&status[0], tag | kSelIncl | (uint64_t)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                counts[1] = 0;  // nvalid, bad, lane-decoder queue, optimistic-decode fallback flag and count:
-                counts[2] = 0;  // zeroed here (later kernels run after this one)
-                counts[3] = 0;
-                counts[6] = 0;  // (ints 4-5 hold the selection ticket)
-                counts[7] = 0;
+                counts[kCntValid] = 0;  // nvalid, bad, lane-decoder queue, optimistic-decode fallback flag and count:
+                counts[kCntBroken] = 0;  // zeroed here (later kernels run after this one)
+                counts[kCntFallback] = 0;
+                counts[kCntDecline] = 0;  // (kCntTicket lies between)
+                counts[kCntOptValid] = 0;
             }
         } else {
             if (lane == 0)
@@ -747,7 +642,7 @@ __global__ void __launch_bounds__(kSelThreads) k_sync_select(const uint8_t *blob
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
         if (lane == 0) {
-            if (ord == nblocks - 1) counts[0] = (int)min<int64_t>(excl + tot, (int64_t)0x7FFFFFFF);
+            if (ord == nblocks - 1) counts[kCntCand] = (int)min<int64_t>(excl + tot, (int64_t)0x7FFFFFFF);
             s_base = excl;
         }
     }
@@ -761,7 +656,6 @@ __global__ void __launch_bounds__(kSelThreads) k_sync_select(const uint8_t *blob
 // scratch), one work-group's scan of the counts, and a placement pass that copies the kept positions to their place;
 // only a block with more candidates than its scratch holds reads its 64 KB again (the range used to be read twice in
 // full: 3.1 GB more per whole-arena decode).
-constexpr int kSelBlkCap = 32;  // candidates kept per 64 KB block (a C4 block holds ~8 frame starts)
 
 // CRC combine of the block's four 16 KB waves (thread 0): WP[w] = CRC of the block's bytes before wave w; returns the
 // block's CRC
@@ -771,7 +665,7 @@ __device__ inline uint32_t sel_crc_block(SelCrcLds *cx) {
 #pragma unroll
     for (int w = 0; w < kSelThreads / 64; w++) {
         cx->WP[w] = pre;
-        pre = dec_gfmul(pre, X) ^ cx->W[w];
+        pre = crc16_mulmod(pre, X) ^ cx->W[w];
     }
     return pre;
 }
@@ -851,7 +745,7 @@ __global__ void k_bound_mark(const int64_t *soff, int ns, int lead, uint32_t *bf
     if (q & (kSelBytes - 1)) atomicMin(&bfirst[q / kSelBytes], (uint32_t)sidx);
 }
 
-// exclusive scan of the block counts in one work-group (bbase[n] = total -> counts[0]); zeroes the later counters
+// exclusive scan of the block counts in one work-group (bbase[n] = total -> counts[kCntCand]); zeroes the later counters
 // CRC (bcrc != nullptr): also BP[i] = CRC of the range's bytes before block i, i = 0 .. n (BP[n]: all n blocks)
 __global__ void __launch_bounds__(1024) k_sync_scan(const int32_t *bcount, int64_t *bbase, int64_t n, int *counts,
                                                   const uint16_t *bcrc = nullptr, uint32_t *BP = nullptr) {
@@ -883,12 +777,12 @@ __global__ void __launch_bounds__(1024) k_sync_scan(const int32_t *bcount, int64
         acc += bcount[i];
     }
     if (t == 0) {
-        counts[0] = (int)min<int64_t>(total, (int64_t)0x7FFFFFFF);
-        counts[1] = 0;
-        counts[2] = 0;
-        counts[3] = 0;
-        counts[6] = 0;  // (ints 4-5 hold the selection ticket)
-        counts[7] = 0;
+        counts[kCntCand] = (int)min<int64_t>(total, (int64_t)0x7FFFFFFF);
+        counts[kCntValid] = 0;
+        counts[kCntBroken] = 0;
+        counts[kCntFallback] = 0;
+        counts[kCntDecline] = 0;  // (kCntTicket lies between)
+        counts[kCntOptValid] = 0;
     }
     if (!bcrc) return;
     // thread t folds blocks [t c, t c + c) (blocks >= n: zeros), Kogge-Stone over the threads with the uniform
@@ -896,26 +790,26 @@ __global__ void __launch_bounds__(1024) k_sync_scan(const int32_t *bcount, int64
     const uint32_t KB = d_xpow_hi[256];
     const int64_t a2 = (int64_t)t * c;
     uint32_t h = 0;
-    for (int64_t i = a2; i < a2 + c; i++) h = dec_gfmul(h, KB) ^ (i < n ? (uint32_t)bcrc[i] : 0u);
+    for (int64_t i = a2; i < a2 + c; i++) h = crc16_mulmod(h, KB) ^ (i < n ? (uint32_t)bcrc[i] : 0u);
     const uint32_t Mc = gf_pow16(KB, (uint64_t)c);  // one thread's span
     uint32_t x2 = h, mo = Mc;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t y = (uint32_t)__shfl_up((int)x2, o);
-        if (lane >= o) x2 = dec_gfmul(y, mo) ^ x2;
-        mo = dec_gfmul(mo, mo);  // Mc^(2o)
+        if (lane >= o) x2 = crc16_mulmod(y, mo) ^ x2;
+        mo = crc16_mulmod(mo, mo);  // Mc^(2o)
     }
     if (lane == 63) wcrc[wv] = x2;  // the wave's 64 c blocks
     __syncthreads();
     const uint32_t M64 = mo;  // Mc^64
     uint32_t pre = 0;
-    for (int k = 0; k < wv; k++) pre = dec_gfmul(pre, M64) ^ wcrc[k];
-    const uint32_t incl = dec_gfmul(pre, gf_pow16(Mc, (uint64_t)(lane + 1))) ^ x2;  // blocks [0, (t + 1) c)
+    for (int k = 0; k < wv; k++) pre = crc16_mulmod(pre, M64) ^ wcrc[k];
+    const uint32_t incl = crc16_mulmod(pre, gf_pow16(Mc, (uint64_t)(lane + 1))) ^ x2;  // blocks [0, (t + 1) c)
     const uint32_t up = (uint32_t)__shfl_up((int)incl, 1);
     uint32_t rc = lane ? up : pre;  // blocks [0, t c)
     for (int64_t i = a2; i < a2 + c && i <= n; i++) {
         BP[i] = rc;
-        if (i < n) rc = dec_gfmul(rc, KB) ^ bcrc[i];
+        if (i < n) rc = crc16_mulmod(rc, KB) ^ bcrc[i];
     }
     if (a2 + c == n) BP[n] = rc;  // (n a multiple of c: no thread's range holds index n)
 }
@@ -997,40 +891,6 @@ __device__ inline void dn_store(const DecOut &o, int64_t i, int32_t pcm, float2 
     case FRS_DT_I32: static_cast<int32_t *>(o.out)[i] = (int32_t)r; break;
     default: static_cast<uint32_t *>(o.out)[i] = (uint32_t)r; break;
     }
-}
-
-// Span check for frames too large for the wave kernel's tables (max frame >= 1 MiB: many channels of
-// 32-bit samples), one thread per candidate: the CRC-16 runs incrementally over the bytes from the
-// candidate, compared at every later candidate start (and the stream end).  Same outputs as
-// k_span_crc_wave: ends[i] = e or -1, nexti[i] = candidate index at e, -2 at the stream end.
-__global__ void k_span_crc(const uint8_t *blob, const int64_t *soff, int ns, const int64_t *cpos, const int *ncand,
-                           int cand_cap, int64_t max_frame, int64_t *ends, int32_t *nexti) {
-    const int nc = *ncand;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (nc > cand_cap || i >= nc) return;
-    const int64_t p = cpos[i];
-    const int s = stream_of(soff, ns, p);
-    const int64_t send = soff[s + 1];
-    const int64_t lim = min(send, p + max_frame);
-    uint32_t crc = 0;  // covers [p, b)
-    int64_t b = p, result = -1;
-    int32_t rnext = -1;
-    for (int j = i + 1;; j++) {
-        int64_t e = j < nc ? cpos[j] : send;
-        if (e > send) e = send;
-        if (e > lim) break;
-        if (e >= p + 7) {
-            for (; b < e - 2; b++) crc = ((crc << 8) & 0xFFFFu) ^ d_crc16[((crc >> 8) ^ blob[b]) & 0xFF];
-            if (crc == (((uint32_t)blob[e - 2] << 8) | blob[e - 1])) {
-                result = e;
-                rnext = (j < nc && cpos[j] < send) ? j : -2;
-                break;
-            }
-        }
-        if (e >= send) break;
-    }
-    ends[i] = result;
-    nexti[i] = rnext;
 }
 
 
@@ -1129,7 +989,7 @@ __global__ void __launch_bounds__(64) k_span_crc_wave(const uint8_t *blob, const
                     }
                     for (; b < b1; b++) c = ((c << 8) & 0xFFFFu) ^ t4[0][((c >> 8) ^ byte_at(b)) & 0xFF];
                     const uint32_t m = nb - b1;  // bytes after this lane's chunk
-                    c = dec_gfmul(dec_gfmul(c, xlo[m & 255]), d_xpow_hi[m >> 8]);
+                    c = crc16_mulmod(crc16_mulmod(c, xlo[m & 255]), d_xpow_hi[m >> 8]);
     #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) c ^= __shfl_xor(c, o);
                     crc = c;
@@ -1292,15 +1152,6 @@ __global__ void __launch_bounds__(256) k_span_pcrc(const int64_t *soff, int ns, 
 // written only once that candidate's CRC span is verified (its link is not -1); frames the walk does not reach
 // get -1 and are skipped by the decoders; any break is counted in *bad.
 constexpr int kChainLds = 4096;
-__device__ inline int lower_bound_pos(const int64_t *cpos, int n, int64_t p) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cpos[mid] < p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 __global__ void __launch_bounds__(1024) k_chain_lds(const int64_t *soff, int ns, const int64_t *cpos, const int *ncand,
                                                    int cand_cap,
                                                    const int32_t *nexti, const int64_t *fbase, int64_t *frame_cand,
@@ -1418,7 +1269,6 @@ __global__ void __launch_bounds__(1024) k_chain_lds(const int64_t *soff, int ns,
     if (!ok) atomicAdd(bad, 1);
 }
 
-constexpr int kDecResMax = 4096;  // residual buffer (LDS) of the fast subframe path
 
 // MSB-first bit reader over global bytes (bounded)
 struct BitReader {
@@ -1901,7 +1751,7 @@ __device__ __attribute__((always_inline)) inline void decode_one_frame(const uin
             }
         }
     }
-    // the decoded subframes must end exactly at the CRC-16 footer found by k_span_crc
+    // the decoded subframes must end exactly at the CRC-16 footer found by the span check
     const int64_t fend = ((br.pos_bits + 7) >> 3) + bits_shift;
     if (br.err || fend + 2 != fend_known) return;
     atomicAdd(nvalid, 1);
@@ -2080,30 +1930,30 @@ __device__ inline void lds_publish(volatile int32_t *p, int32_t v) {
 }
 __device__ inline int32_t lds_poll(volatile int32_t *p) { return *p; }
 
-// OPT: the last work-group to finish (flags[8] counts them; re-armed to 0) copies the call's counters flags[0..7] to
+// OPT: the last work-group to finish (flags[kCntRearm] counts them; re-armed to 0) copies the call's counters flags[0, kCntHostWords) to
 // page-locked host memory, so the host reads them after its stream synchronisation without a device-to-host copy
-// (system-scope fences: the work-group's output may be page-locked host memory, and the host takes hout[6] leaving -1
+// (system-scope fences: the work-group's output may be page-locked host memory, and the host takes hout[kCntDecline] leaving -1
 // as the decode's completion -- it is written last, after every other counter)
 __device__ inline void pipe_wg_exit(int *flags, int64_t nframes, int *hout) {
     __threadfence_system();
-    const int t = atomicAdd(&flags[8], 1);
+    const int t = atomicAdd(&flags[kCntRearm], 1);
     if (t == (int)nframes - 1) {
-        flags[8] = 0;
+        flags[kCntRearm] = 0;
         __threadfence();
-        for (int k = 0; k < 8; k++)
-            if (k != 6) hout[k] = __hip_atomic_load(&flags[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int h6 = __hip_atomic_load(&flags[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int k = 0; k < kCntHostWords; k++)
+            if (k != kCntDecline) hout[k] = __hip_atomic_load(&flags[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int h6 = __hip_atomic_load(&flags[kCntDecline], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence_system();
-        __hip_atomic_store(&hout[6], h6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&hout[kCntDecline], h6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __threadfence_system();
     }
 }
 // OPT (small ranges, launched right after the selection): the optimistic form -- when the selection found exactly
 // one candidate per frame and each stream's first at its first byte, frame i IS candidate i and its span ends at
 // candidate i + 1 (or the stream end), so the span check and the chain are skipped: the consumer wave checks the
-// span's CRC-16 over the staged bytes while the producer parses, and a frame counts (flags[7]) only when its CRC and
+// span's CRC-16 over the staged bytes while the producer parses, and a frame counts (flags[kCntOptValid]) only when its CRC and
 // its end both verify.  Anything else (a false sync, a frame the producer would hand to the one-lane decoder) sets
-// flags[6], and the host runs the span check, chain and the non-optimistic decoder after all.
+// flags[kCntDecline], and the host runs the span check, chain and the non-optimistic decoder after all.
 template <bool OPT = false>
 __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob, const int64_t *soff, int ns,
                                                            const int64_t *poff, const int64_t *cpos,
@@ -2148,7 +1998,7 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
                 fend_known <= soff[s + 1];
         if (!okmap) {
             if (threadIdx.x == 0) {
-                atomicOr(&flags[6], 1);
+                atomicOr(&flags[kCntDecline], 1);
                 __threadfence();
             }
             __syncthreads();
@@ -2241,7 +2091,7 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
         };
         if (OPT && !staged) {  // (the one-lane decoder needs the verified chain)
             if (lane == 0) {
-                atomicOr(&flags[6], 1);
+                atomicOr(&flags[kCntDecline], 1);
                 __threadfence();
             }
             finish(kPipeError, 0);
@@ -2276,7 +2126,7 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
         auto fallback = [&]() {
             if (OPT) {
                 if (lane == 0) {
-                    atomicOr(&flags[6], 1);
+                    atomicOr(&flags[kCntDecline], 1);
                     __threadfence();
                 }
                 finish(kPipeError, 0);
@@ -2642,7 +2492,7 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
         if constexpr (OPT) {
             while (lds_poll(&vi->finished) == 0) __builtin_amdgcn_s_sleep(1);
             __asm__ volatile("" ::: "memory");
-            if (st == kPipeDone && info.valid && info.crc_ok && lane == 0) atomicAdd(&flags[7], 1);
+            if (st == kPipeDone && info.valid && info.crc_ok && lane == 0) atomicAdd(&flags[kCntOptValid], 1);
             if (lane == 0) pipe_wg_exit(flags, nframes, hout);
         }
         return;
@@ -2836,7 +2686,7 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
         for (int i = lane; i < bs; i += 64) put(i, (int32_t)((uint32_t)(int32_t)x16[i] << w));
     }
     if (lane == 0) {
-        atomicAdd(OPT ? &flags[7] : nvalid, 1);
+        atomicAdd(OPT ? &flags[kCntOptValid] : nvalid, 1);
         if (OPT) pipe_wg_exit(flags, nframes, hout);
     }
 }
@@ -3385,418 +3235,378 @@ __global__ void k_denormalize(const int32_t *pcm, int64_t n, int shift, float rn
     out[i] = (O)(int64_t)r;
 }
 
+// ------------------------------------------------------------------------------------------------ host
+// decode_job plans a call (plan_decode_route) and runs the stages below in order; each returns an frs error code.
 static bool g_dec_tables[64];
-constexpr int64_t kLaneMinFrames = 4096;
-constexpr int64_t kSelOnePassBlocks = 256;  // up to 16 MB: the one-pass selection (latency: C5 queries)  // below: the pipelined decoder (C5 queries decode 64 frames)
+
+// One decode_job call (a stack value): its arguments, its route and the pointers its stages share
+struct DecodeCall {
+    const uint8_t *blob;
+    int64_t blob_bytes, frames;
+    int32_t nstreams, channels, bps, blocksize;
+    int32_t *pcm;
+    DecodeRoute r;
+    DecOut dout;
+    SmallTabs stabs;  // tabs_by_arg: the per-call tables as a kernel argument
+    int *hv, *cnt;    // the counters word (DecCounter): pinned host copy (after the staged tables), device
+    int64_t *dsoff, *dfbase, *dpoff, *dchain;  // device: stream_off | fbase | pcm_off | dn pairs | frame -> candidate
+    int64_t *cpos, *ends;  // candidates: position, end of the verified span
+    int32_t *nexti;        // candidate at the span's end
+    uint32_t *BP;          // SpanForm::Pcrc (PcrcLayout)
+    uint16_t *sbib, *pcrc;
+    int lead() const { return (int)(reinterpret_cast<uintptr_t>(blob) & 15); }
+};
+
+// The CRC tables, once per device
+static int init_decode_tables(frs_ctx *ctx) {
+    if (g_dec_tables[ctx->device]) return FRS_OK;
+    hipStream_t st = ctx->stream;
+    uint8_t t8[256];
+    crc8_table(t8);
+    // slice-by-16: T[j][v] = CRC-16 of byte v followed by j zero bytes = v x^(16 + 8j); T[0] is the byte table and
+    // T[0..3] the slice-by-4 tables
+    static uint16_t sct[kSelCrcTab], lo[kDecXpowLo], hi[kDecXpowHi];
+    uint16_t *T = sct, *MK = sct + 16 * 256, *ML = sct + 18 * 256;
+    for (int v = 0; v < 256; v++) {
+        uint32_t c = crc16_mulmod((uint32_t)v << 8, 0x100);
+        for (int j = 0; j < 16; j++, c = crc16_mulmod(c, 0x100)) T[256 * j + v] = (uint16_t)c;
+    }
+    // prefix-CRC selection tables: x^(8 * 1024) (one step), x^(8 * 16 * 2^i) (lane tree level i)
+    auto split = [](uint16_t *M, uint32_t K) {  // multiply by K, byte-split: M[v] = (v x^8) K, M[256 + v] = v K
+        for (int v = 0; v < 256; v++) {
+            M[v] = (uint16_t)crc16_mulmod((uint32_t)v << 8, K);
+            M[256 + v] = (uint16_t)crc16_mulmod((uint32_t)v, K);
+        }
+    };
+    split(MK, crc16_xpow(8 * 1024));
+    for (int i = 0; i < 6; i++) split(ML + 512 * i, crc16_xpow(8 * (16 << i)));
+    for (int m = 0; m < kDecXpowLo; m++) lo[m] = (uint16_t)crc16_xpow(8l * m);
+    for (int m = 0; m < kDecXpowHi; m++) hi[m] = (uint16_t)crc16_xpow(8l * kDecXpowLo * m);
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_crc8), t8, sizeof(t8), 0, hipMemcpyHostToDevice, st));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_crc16), T, 2 * 256, 0, hipMemcpyHostToDevice, st));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_crc16x4), T, 2 * 4 * 256, 0, hipMemcpyHostToDevice, st));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_selcrc_tab), sct, sizeof(sct), 0, hipMemcpyHostToDevice, st));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_xpow_lo), lo, sizeof(lo), 0, hipMemcpyHostToDevice, st));
+    FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_xpow_hi), hi, sizeof(hi), 0, hipMemcpyHostToDevice, st));
+    FRS_HIP(hipStreamSynchronize(st));
+    g_dec_tables[ctx->device] = true;
+    return FRS_OK;
+}
+
+// The call's scratch (the int32 PCM scratch, the candidate buffers, the counters word, the one-pass status words)
+// and its tables
+static int stage_decode_tables(frs_ctx *ctx, DecodeCall &c, const int64_t *stream_off, const int64_t *fbase,
+                               const int64_t *pcm_off, const double *dmin, const double *dmax, int32_t out_dtype,
+                               void *out_dev) {
+    hipStream_t st = ctx->stream;
+    const DecodeRoute &r = c.r;
+    const int ns = c.nstreams;
+    // every decoder but the pipelined one de-normalises out of an int32 scratch
+    if (r.fused && r.dec != FrameDec::Pipe && !c.pcm) {
+        const int64_t nsamp_all = pcm_off[c.nstreams] - pcm_off[0];
+        FRS_HIP(ctx->dec_pcm.ensure((size_t)std::max(nsamp_all * c.channels, r.planar_words) * 4 + 16));
+        c.pcm = ctx->dec_pcm.as<int32_t>() - pcm_off[0] * c.channels;
+    }
+    // (the planar scratch is consumed by k_interleave_dn before the fallback decoder reuses dec_pcm)
+    if (r.dec == FrameDec::MultiLane && !r.fused) FRS_HIP(ctx->dec_pcm.ensure((size_t)r.planar_words * 4 + 16));
+    FRS_HIP(ctx->dec_cand.ensure(sizeof(int64_t) * 2 * (size_t)r.cand_cap));
+    FRS_HIP(ctx->dec_next.ensure(sizeof(int32_t) * (size_t)r.cand_cap + 64));
+    if (!ctx->dec_count.ptr) {  // counters + the selection ticket: zeroed once, re-armed by the kernels
+        FRS_HIP(ctx->dec_count.ensure(64));
+        FRS_HIP(hipMemsetAsync(ctx->dec_count.ptr, 0, ctx->dec_count.bytes, st));
+    }
+    // a grown buffer may come back at the same address with stale words (possibly of the current epoch), and an
+    // epoch that wraps could match an old word: zero the status words in both cases
+    const size_t before = ctx->dec_status.bytes;
+    FRS_HIP(ctx->dec_status.ensure(sizeof(uint64_t) * (size_t)std::min<int64_t>(r.nblocks, kSelOnePassBlocks)));
+    const bool wrap = ++ctx->dec_epoch >= (1u << 24);
+    if (wrap) ctx->dec_epoch = 1;
+    if (ctx->dec_status.bytes != before || wrap)
+        FRS_HIP(hipMemsetAsync(ctx->dec_status.ptr, 0, ctx->dec_status.bytes, st));
+    c.cnt = ctx->dec_count.as<int>();
+    c.cpos = ctx->dec_cand.as<int64_t>();
+    c.ends = c.cpos + r.cand_cap;
+    c.nexti = ctx->dec_next.as<int32_t>();
+    // the per-call tables through the context's pinned staging in one DMA copy: stream_off | fbase | pcm_off | the
+    // fused decode's per-stream (float32(max - min), float32(min)) pairs; the result counters come back after them
+    // (hv).  tabs_by_arg: no copy, they ride in the selection kernel's arguments, and block 0 writes them to dsoff
+    const size_t tab = sizeof(int64_t) * (size_t)(ns + 1);
+    const size_t dn_bytes = r.fused ? sizeof(float2) * (size_t)ns : 0;
+    FRS_HIP(ctx->dec_soff.ensure(3 * tab + dn_bytes + sizeof(int64_t) * c.frames + 64));
+    FRS_HIP(ctx->pin.ensure(3 * tab + dn_bytes + 128));
+    int64_t *htab = ctx->pin.at<int64_t>(0);
+    memcpy(htab, stream_off, tab);
+    memcpy(htab + (ns + 1), fbase, tab);
+    memcpy(htab + 2 * (ns + 1), pcm_off, tab);
+    float2 *hdn = reinterpret_cast<float2 *>(htab + 3 * (ns + 1));
+    if (r.fused)  // python-float arithmetic first (data_max - data_min in double), then NEP 50 casts to float32
+        for (int s = 0; s < ns; s++) hdn[s] = make_float2((float)(dmax[s] - dmin[s]), (float)dmin[s]);
+    if (r.tabs_by_arg) memcpy(c.stabs.v, htab, 3 * tab + dn_bytes);  // 6 int64 + one float2
+    else FRS_HIP(hipMemcpyAsync(ctx->dec_soff.ptr, htab, 3 * tab + dn_bytes, hipMemcpyHostToDevice, st));
+    c.hv = reinterpret_cast<int *>(reinterpret_cast<char *>(htab) + ((3 * tab + dn_bytes + 15) & ~(size_t)15));
+    c.dsoff = ctx->dec_soff.as<int64_t>();
+    c.dfbase = c.dsoff + (ns + 1);
+    c.dpoff = c.dfbase + (ns + 1);
+    c.dchain = reinterpret_cast<int64_t *>((reinterpret_cast<uintptr_t>(c.dpoff + (ns + 1)) + dn_bytes + 7) & ~(uintptr_t)7);
+    c.dout = {out_dev, reinterpret_cast<const float2 *>(c.dpoff + (ns + 1)), out_dtype, c.bps > 16 ? 16 : 0};
+    return FRS_OK;
+}
+
+// Candidate selection ("decode" in the profile); SpanForm::Pcrc: with the prefix CRCs folded in
+static int launch_selection(frs_ctx *ctx, DecodeCall &c) {
+    hipStream_t st = ctx->stream;
+    const DecodeRoute &r = c.r;
+    const int ns = c.nstreams;
+    const unsigned nblocks = (unsigned)r.nblocks, nfull = (unsigned)r.nfull;
+    hipEvent_t ev;
+    prof_begin(ctx, "decode", &ev);
+    if (r.sel != SelForm::TwoPass) {
+#define FRS_SELECT(STEPS)                                                                                            \
+    k_sync_select<STEPS><<<nblocks, kSelThreads, 0, st>>>(                                                           \
+        c.blob, c.blob_bytes, c.dsoff, ns, c.channels, c.bps, ctx->dec_status.as<uint64_t>(),                        \
+        reinterpret_cast<unsigned long long *>(c.cnt + kCntTicket), ctx->dec_epoch, r.nblocks, c.cpos, r.cand_cap,   \
+        c.cnt, r.tabs_by_arg ? c.dsoff : nullptr, c.stabs)
+        if (r.sel == SelForm::OnePassSmall) FRS_SELECT(kSelStepsSmall);
+        else FRS_SELECT(kSelSteps);
+#undef FRS_SELECT
+    } else {
+        // (its own buffer: the one-pass status words must keep their epoch tags)
+        const SelLayout sl = sel_layout(r.nblocks);
+        FRS_HIP(ctx->dec_sel.ensure(sl.total));
+        int32_t *bcount = ctx->dec_sel.at<int32_t>(sl.bcount);
+        int64_t *bbase = ctx->dec_sel.at<int64_t>(sl.bbase), *bpos = ctx->dec_sel.at<int64_t>(sl.bpos);
+        const bool pcrc = r.span == SpanForm::Pcrc;
+        uint32_t *bfirst = nullptr;  // (the reading form passes null pointers for the CRC buffers)
+        uint16_t *bcrc = nullptr, *bipc = nullptr;
+        if (pcrc) {
+            const PcrcLayout pl = pcrc_layout(r.nblocks, ns, r.cand_cap);
+            FRS_HIP(ctx->dec_crc.ensure(pl.total));
+            const DevBuf &crc = ctx->dec_crc;
+            c.BP = crc.at<uint32_t>(pl.bp), bfirst = crc.at<uint32_t>(pl.bfirst);
+            bcrc = crc.at<uint16_t>(pl.bcrc), bipc = crc.at<uint16_t>(pl.bipc);
+            c.sbib = crc.at<uint16_t>(pl.sbib), c.pcrc = crc.at<uint16_t>(pl.pcrc);
+            FRS_HIP(hipMemsetAsync(bfirst, 0xFF, pl.bcrc - pl.bfirst, st));
+            k_bound_mark<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(c.dsoff, ns, c.lead(), bfirst);
+        }
+        // blocks whose 64 KB lie inside the range take the unguarded instance; the last, partial block its own launch
+        auto run = [&](auto crc) {
+            constexpr bool CRC = decltype(crc)::value;
+            if (nfull)
+                k_sync_count<CRC, true><<<nfull, kSelThreads, 0, st>>>(c.blob, c.blob_bytes, c.dsoff, ns, c.channels,
+                                                                       c.bps, bcount, bpos, bcrc, bipc, bfirst, c.sbib, 0);
+            if (nblocks > nfull)
+                k_sync_count<CRC, false><<<nblocks - nfull, kSelThreads, 0, st>>>(
+                    c.blob, c.blob_bytes, c.dsoff, ns, c.channels, c.bps, bcount, bpos, bcrc, bipc, bfirst, c.sbib, r.nfull);
+            k_sync_scan<<<1, 1024, 0, st>>>(bcount, bbase, r.nblocks, c.cnt, bcrc, c.BP);
+            k_sync_scatter<CRC><<<nblocks, kSelThreads, 0, st>>>(c.blob, c.blob_bytes, c.dsoff, ns, c.channels, c.bps,
+                                                                 bbase, c.cpos, r.cand_cap, bcount, bpos, c.pcrc, c.BP,
+                                                                 bipc);
+        };
+        if (pcrc) run(std::true_type{});
+        else run(std::false_type{});
+    }
+    prof_end(ctx, "decode", ev);
+    return FRS_OK;
+}
+
+// Small mono ranges (C5 queries): the optimistic pipe decode right after the selection (no span check, no chain).
+// *done: it decoded every frame, or failed (the return value says which); otherwise it declined (kCntDecline: a false
+// sync, a frame for the one-lane decoder) and the span check, chain and decoder run after this one more host round
+// trip
+static int decode_optimistic(frs_ctx *ctx, DecodeCall &c, bool *done) {
+    hipStream_t st = ctx->stream;
+    int *hv = c.hv;
+    // the last work-group copies the counters into hv (page-locked) itself: no device-to-host copy to wait for
+    hv[kCntDecline] = -1;
+    hipEvent_t ev;
+    prof_begin(ctx, "decode_frames", &ev);
+    k_decode_frames_pipe<true><<<(unsigned)c.frames, 192, 0, st>>>(
+        c.blob, c.dsoff, c.nstreams, c.dpoff, c.cpos, c.ends, c.dfbase, c.dchain, c.frames, c.channels, c.bps, c.pcm,
+        c.blocksize, c.cnt + kCntValid, c.dout, c.cnt + kCntCand, c.cnt, hv);
+    prof_end(ctx, "decode_frames", ev);
+    FRS_HIP(hipGetLastError());
+    // completion = the last work-group's page-locked counters (hv[kCntDecline] written last, after system-scope
+    // fences over every work-group's output): polled here, a few microseconds before the stream's completion signal;
+    // bounded, then the stream synchronisation decides.  FRS_C5_POLL=0: synchronise only
+    static const bool poll = !(getenv("FRS_C5_POLL") && atoi(getenv("FRS_C5_POLL")) == 0);
+    bool seen = false;
+    if (poll && !ctx->prof) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t k = 0; !seen; k++) {
+            seen = __atomic_load_n(&hv[kCntDecline], __ATOMIC_ACQUIRE) != -1;
+            if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
+        }
+    }
+    if (!seen) FRS_HIP(hipStreamSynchronize(st));
+    if (__atomic_load_n(&hv[kCntDecline], __ATOMIC_ACQUIRE) == -1) {  // (not expected) the epilogue did not run: copy, re-arm
+        FRS_HIP(hipMemcpyAsync(hv, c.cnt, sizeof(int) * kCntHostWords, hipMemcpyDeviceToHost, st));
+        FRS_HIP(hipMemsetAsync(c.cnt + kCntRearm, 0, sizeof(int), st));
+        FRS_HIP(hipStreamSynchronize(st));
+        if (hv[kCntDecline] == 0) hv[kCntDecline] = 1;  // decide by the full path
+    }
+    if (hv[kCntDecline] != 0) return FRS_OK;
+    *done = true;
+    // the early completion covers output in page-locked host memory (the kernels' system-scope fences); a
+    // device-memory output is complete in the stream's order only: synchronise for it
+    if (seen) {
+        if (c.dout.out && ctx->is_host_alloc(c.dout.out, 1)) ctx->unsynced = true;
+        else FRS_HIP(hipStreamSynchronize(st));
+    }
+    prof_collect(ctx);
+    if (hv[kCntOptValid] != c.frames) {
+        ctx->err = "decoded " + std::to_string(hv[kCntOptValid]) + " valid frames, expected " + std::to_string(c.frames);
+        return FRS_E_CORRUPT;
+    }
+    return FRS_OK;
+}
+
+// Span check and chain ("decode_span").  An overflowing selection makes every later kernel a no-op and is reported
+// by finish_decode
+static int launch_span_and_chain(frs_ctx *ctx, DecodeCall &c) {
+    hipStream_t st = ctx->stream;
+    const DecodeRoute &r = c.r;
+    const int ns = c.nstreams, cap = (int)r.cand_cap;
+    const int *ncand = c.cnt + kCntCand;
+    // launched before the host knows the candidate count (no mid-query sync): an upper-bound grid strides over *ncand
+    const int64_t bound = std::min<int64_t>(r.cand_cap, 2 * c.frames + 256);
+    const unsigned lanes = (unsigned)((bound + 255) / 256), waves = (unsigned)std::min<int64_t>(bound, ctx->num_cus * 64);
+    hipEvent_t ev;
+    prof_begin(ctx, "decode_span", &ev);
+    if (r.span == SpanForm::Pcrc)
+        k_span_pcrc<<<lanes, 256, 0, st>>>(c.dsoff, ns, c.cpos, ncand, cap, r.max_frame, c.pcrc, c.BP, c.sbib, c.lead(),
+                                           c.ends, c.nexti);
+    else if (r.span == SpanForm::Lane)
+        k_span_crc_lane<<<lanes, 256, 0, st>>>(c.blob, c.dsoff, ns, c.cpos, ncand, cap, r.max_frame, c.ends, c.nexti);
+    else  // (FrameDec::Pipe: max_frame is within the x^(8m) tables of the wave CRC)
+        k_span_crc_wave<<<waves, 64, 0, st>>>(c.blob, c.dsoff, ns, c.cpos, ncand, cap, r.max_frame, c.ends, c.nexti);
+    k_chain_lds<<<ns, ns == 1 ? 1024 : 64, 0, st>>>(c.dsoff, ns, c.cpos, ncand, cap, c.nexti, c.dfbase, c.dchain,
+                                                     c.cnt + kCntBroken);
+    prof_end(ctx, "decode_span", ev);
+    return FRS_OK;
+}
+
+// The frame decoder of the route ("decode_frames"; "decode_fallback" after a declined optimistic decode); the lane
+// decoders' fallback list goes through k_decode_frames_wave_list
+static int launch_frame_decoders(frs_ctx *ctx, DecodeCall &c) {
+    hipStream_t st = ctx->stream;
+    const DecodeRoute &r = c.r;
+    const char *name = r.pipe_opt ? "decode_fallback" : "decode_frames";
+    int *nvalid = c.cnt + kCntValid, *fbc = c.cnt + kCntFallback;
+    const bool lanes = r.dec == FrameDec::Lane || r.dec == FrameDec::MultiLane;
+    const unsigned lg = (unsigned)((c.frames + 255) / 256);
+    int32_t *fbl = nullptr, *planar = ctx->dec_pcm.as<int32_t>();
+    int8_t *fchass = nullptr;
+    hipEvent_t ev;
+    prof_begin(ctx, name, &ev);
+    if (lanes) {
+        FRS_HIP(ctx->dec_fb.ensure(sizeof(int32_t) * (size_t)c.frames + 64));
+        fbl = ctx->dec_fb.as<int32_t>();
+    }
+#define FRS_FRAMES c.blob, c.dsoff, c.nstreams, c.dpoff, c.cpos, c.ends, c.dfbase, c.dchain  // every decoder's first arguments
+#define FRS_OUT c.bps, c.pcm, c.blocksize, nvalid, c.dout
+#define FRS_LANE(K) k_decode_frames_lane<K><<<lg, 256, lane_lds, st>>>(FRS_FRAMES, c.frames, FRS_OUT, fbl, fbc)
+#define FRS_MULTI(K) \
+    k_decode_frames_lane<K, true><<<lg, 256, 0, st>>>(FRS_FRAMES, c.frames, FRS_OUT, fbl, fbc, c.channels, planar, fchass)
+    switch (r.dec) {
+    case FrameDec::Lane: {
+        // (experiment) FRS_DEC_LANE_LDS: dynamic LDS per work-group, i.e. a cap on the lane decoder's occupancy
+        static const size_t lane_lds = getenv("FRS_DEC_LANE_LDS") ? (size_t)atol(getenv("FRS_DEC_LANE_LDS")) : 0;
+        switch (r.fused ? c.dout.dtype : -1) {
+        case -1: FRS_LANE(kOutPcm); break;
+        case FRS_DT_I16: FRS_LANE(kOutI16); break;
+        case FRS_DT_U16: FRS_LANE(kOutU16); break;
+        case FRS_DT_U8: FRS_LANE(kOutU8); break;
+        default: FRS_LANE(kOutAny); break;
+        }
+        break;
+    }
+    case FrameDec::MultiLane: {
+        if (c.channels == 2) {
+            FRS_HIP(ctx->dec_chass.ensure((size_t)c.frames + 64));
+            fchass = ctx->dec_chass.as<int8_t>();
+        }
+        if (r.planar16) FRS_MULTI(kOutPlanar16);
+        else FRS_MULTI(kOutPcm);
+        const int cpf = (c.blocksize + 255) / 256;
+        k_interleave_dn<<<(unsigned)(c.frames * cpf), 256, 0, st>>>(planar, c.dpoff, c.dfbase, c.nstreams, c.channels,
+                                                                 c.blocksize, c.pcm, c.dout, fchass, cpf,
+                                                                 (int)r.planar16);
+        break;
+    }
+    case FrameDec::Pipe:
+        k_decode_frames_pipe<<<(unsigned)c.frames, 192, 0, st>>>(FRS_FRAMES, c.frames, c.channels, FRS_OUT);
+        break;
+    case FrameDec::Wave:
+        k_decode_frames_wave<<<(unsigned)c.frames, 64, 0, st>>>(FRS_FRAMES, c.frames, c.channels, FRS_OUT);
+        break;
+    }
+    if (lanes)
+        k_decode_frames_wave_list<<<(unsigned)std::min<int64_t>(c.frames, 4 * (int64_t)ctx->num_cus), 64, 0, st>>>(
+            FRS_FRAMES, c.channels, FRS_OUT, fbl, fbc);
+#undef FRS_MULTI
+#undef FRS_OUT
+#undef FRS_LANE
+#undef FRS_FRAMES
+    prof_end(ctx, name, ev);
+    FRS_HIP(hipGetLastError());
+    return FRS_OK;
+}
+
+// The counters back, the profile's lane_fallback_frames, the verdict
+static int finish_decode(frs_ctx *ctx, DecodeCall &c) {
+    const int *hv = c.hv;
+    FRS_HIP(hipMemcpyAsync(c.hv, c.cnt, sizeof(int) * kCntHostWords, hipMemcpyDeviceToHost, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    const bool lanes = c.r.dec == FrameDec::Lane || c.r.dec == FrameDec::MultiLane;
+    if (ctx->prof && lanes) {  // frames the lane decoder handed to the wave decoder (profile_avg_ms of this name)
+        ProfEntry &e = ctx->prof_tab["lane_fallback_frames"];
+        e.total_ms += hv[kCntFallback];
+        e.count += 1;
+    }
+    if ((int64_t)hv[kCntCand] > c.r.cand_cap) {
+        ctx->err = "too many frame sync candidates (" + std::to_string(hv[kCntCand]) + " > " +
+                   std::to_string(c.r.cand_cap) + "): not a FLAC stream of the expected layout";
+        return FRS_E_CORRUPT;
+    }
+    if (hv[kCntBroken] != 0 || hv[kCntValid] != c.frames) {
+        ctx->err = "decoded " + std::to_string(hv[kCntValid]) + " valid frames, expected " + std::to_string(c.frames) +
+                   (hv[kCntBroken] ? " (broken frame chain)" : "");
+        return FRS_E_CORRUPT;
+    }
+    return FRS_OK;
+}
 
 int decode_job(frs_ctx *ctx, const uint8_t *blob_dev, int64_t blob_bytes, const int64_t *stream_off,
                int32_t nstreams, int32_t channels, int32_t bps, int32_t blocksize, int32_t *pcm_dev,
                const int64_t *pcm_off, const double *dmin, const double *dmax, int32_t out_dtype, void *out_dev) {
-    hipStream_t st = ctx->stream;
     if (const int rc = check_unsynced(ctx)) return rc;
-    if (!g_dec_tables[ctx->device]) {
-        uint8_t t8[256];
-        uint16_t t16[256];
-        for (int i = 0; i < 256; i++) {
-            uint8_t c = (uint8_t)i;
-            for (int k = 0; k < 8; k++) c = (c & 0x80) ? (uint8_t)((c << 1) ^ 0x07) : (uint8_t)(c << 1);
-            t8[i] = c;
-            uint16_t d = (uint16_t)(i << 8);
-            for (int k = 0; k < 8; k++) d = (d & 0x8000) ? (uint16_t)((d << 1) ^ 0x8005) : (uint16_t)(d << 1);
-            t16[i] = d;
-        }
-        FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_crc8), t8, sizeof(t8), 0, hipMemcpyHostToDevice, st));
-        FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_crc16), t16, sizeof(t16), 0, hipMemcpyHostToDevice, st));
-        static uint16_t t16x4[4][256];
-        for (int i = 0; i < 256; i++) {
-            uint16_t c = t16[i];
-            t16x4[0][i] = c;
-            for (int j = 1; j < 4; j++) {
-                c = (uint16_t)(((c << 8) & 0xFFFF) ^ t16[c >> 8]);
-                t16x4[j][i] = c;
-            }
-        }
-        FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_crc16x4), t16x4, sizeof(t16x4), 0, hipMemcpyHostToDevice, st));
-        auto mulmod = [](uint32_t a, uint32_t b) {
-            uint32_t r = 0;
-            for (int i = 15; i >= 0; i--) {
-                r <<= 1;
-                if (r & 0x10000u) r ^= 0x18005u;
-                if ((b >> i) & 1u) r ^= a;
-            }
-            return r;
-        };
-        static uint16_t lo[256], hi[4096];
-        uint32_t pw = 1;
-        for (int m = 0; m < 256; m++) {
-            lo[m] = (uint16_t)pw;
-            pw = mulmod(pw, 0x100);
-        }
-        const uint32_t step = pw;  // x^(8*256)
-        pw = 1;
-        for (int m = 0; m < 4096; m++) {
-            hi[m] = (uint16_t)pw;
-            pw = mulmod(pw, step);
-        }
-        // prefix-CRC selection tables: slice-by-16, x^(8 * 1024), x^(8 * 16 * 2^i) as byte-split multipliers
-        static uint16_t sct[kSelCrcTab];
-        {
-            uint16_t *T = sct, *MK = sct + 16 * 256, *ML = sct + 18 * 256;
-            for (int i = 0; i < 256; i++) {
-                uint16_t c = t16[i];
-                T[i] = c;
-                for (int j = 1; j < 16; j++) {
-                    c = (uint16_t)(((c << 8) & 0xFFFF) ^ t16[c >> 8]);
-                    T[256 * j + i] = c;
-                }
-            }
-            auto xpow8 = [&](uint64_t m) {  // x^(8m) mod P
-                uint32_t r = 1, b = 0x100;
-                while (m) {
-                    if (m & 1) r = mulmod(r, b);
-                    b = mulmod(b, b);
-                    m >>= 1;
-                }
-                return r;
-            };
-            auto split = [&](uint16_t *M, uint32_t K) {
-                for (int v = 0; v < 256; v++) {
-                    M[v] = (uint16_t)mulmod((uint32_t)v << 8, K);
-                    M[256 + v] = (uint16_t)mulmod((uint32_t)v, K);
-                }
-            };
-            split(MK, xpow8(1024));
-            for (int i = 0; i < 6; i++) split(ML + 512 * i, xpow8(16u << i));
-        }
-        FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_selcrc_tab), sct, sizeof(sct), 0, hipMemcpyHostToDevice, st));
-        FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_xpow_lo), lo, sizeof(lo), 0, hipMemcpyHostToDevice, st));
-        FRS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(d_xpow_hi), hi, sizeof(hi), 0, hipMemcpyHostToDevice, st));
-        FRS_HIP(hipStreamSynchronize(st));
-        g_dec_tables[ctx->device] = true;
-    }
+    if (const int rc = init_decode_tables(ctx)) return rc;
     if (blob_bytes <= 0 || nstreams <= 0) return FRS_OK;
-    const bool fused = out_dev != nullptr;
     std::vector<int64_t> fbase(nstreams + 1, 0);
     for (int s = 0; s < nstreams; s++) fbase[s + 1] = fbase[s] + (pcm_off[s + 1] - pcm_off[s] + blocksize - 1) / blocksize;
-    const int64_t frames = fbase[nstreams];
-    if (frames == 0) return FRS_OK;
-    const int64_t max_frame = (int64_t)blocksize * channels * 5 + 4096;
-    // FRS_FORCE_GENERIC (tests): every frame through the one-lane wave decoder
-    const bool pipe = channels == 1 && bps <= 16 && blocksize <= kDecResMax && !ctx->force_generic;
-    // many mono frames: the lane-per-frame throughput decoder (the pipelined one is latency-optimised: ~2 work-groups
-    // per CU at 62 KB of LDS each); FRS_DECODE_LANE=0/1 overrides for tests
-    bool lane = pipe && frames >= kLaneMinFrames;
-    if (ctx->decode_lane >= 0) lane = pipe && ctx->decode_lane == 1;
-    // multi-channel streams (>= 3 independent channels, 16-bit): the lane decoder walks each frame's subframes into a
-    // channel-planar int32 scratch, k_interleave_dn interleaves (and de-normalises); the wave decoder takes the rest
-    const bool mcl = channels >= 2 && channels <= 8 && bps <= 16 && blocksize <= kDecResMax && !ctx->force_generic &&
-                     frames >= 64 && ctx->decode_lane != 0;
-    const int64_t nsamp_all = pcm_off[nstreams] - pcm_off[0];
-    const int64_t planar_words = mcl ? frames * channels * (int64_t)blocksize : 0;
-    if (fused && (!pipe || lane)) {  // the wave decoder de-normalises out of an int32 scratch
-        if (!pcm_dev) {
-            FRS_HIP(ctx->dec_pcm.ensure((size_t)std::max(nsamp_all * channels, planar_words) * 4 + 16));
-            pcm_dev = ctx->dec_pcm.as<int32_t>() - pcm_off[0] * channels;
-        }
-    }
-    if (mcl && !fused) FRS_HIP(ctx->dec_pcm.ensure((size_t)planar_words * 4 + 16));
-    // (the planar scratch is consumed by k_interleave_dn before the fallback decoder reuses dec_pcm)
-    // Candidate capacity: every true frame plus false syncs (a sync pattern with a CRC-8-correct header inside
-    // frame data, ~1e-7 per byte) with a wide margin; a crafted stream with more is rejected (nothing is written
-    // past the cap).  Indices stay below 2^31.
-    const int64_t cand_cap = std::min<int64_t>(2 * frames + blob_bytes / 1024 + 4096, (int64_t)0x7FFFFFF0);
-    const int64_t lead_bytes = blob_bytes + (int64_t)(reinterpret_cast<uintptr_t>(blob_dev) & 15);
-    const int64_t kSmallBytes = (int64_t)kSelStepsSmall * 1024 * (kSelThreads / 64);
-    const bool sel_small = (lead_bytes + kSmallBytes - 1) / kSmallBytes <= kSelOnePassBlocks;
-    const int64_t sel_bytes = sel_small ? kSmallBytes : kSelBytes;
-    const int64_t nblocks = (lead_bytes + sel_bytes - 1) / sel_bytes;
-    if (nblocks > (int64_t)0xFFFFFFFF) {
+    if (fbase[nstreams] == 0) return FRS_OK;
+    DecodeCall c = {blob_dev, blob_bytes, fbase[nstreams], nstreams, channels, bps, blocksize, pcm_dev};
+    // FRS_SPAN_READ=1 / 2 forces the reading / prefix-CRC span check of a two-pass selection (tests): read per call,
+    // but not for a range of the small one-pass form (no env walk per C5 query), which would ignore it
+    const char *span_env = blob_bytes > kSelOnePassBlocks * kSelSmallBytes ? getenv("FRS_SPAN_READ") : nullptr;
+    c.r = plan_decode_route(channels, bps, blocksize, c.frames, nstreams, blob_bytes, c.lead(), ctx->force_generic,
+                            ctx->decode_lane, ctx->pipe_opt, span_env ? atoi(span_env) : 0, out_dev != nullptr);
+    if (c.r.nblocks > (int64_t)0xFFFFFFFF) {
         ctx->err = "decode range too large";
         return FRS_E_UNSUPPORTED;
     }
-    FRS_HIP(ctx->dec_cand.ensure(sizeof(int64_t) * 2 * (size_t)cand_cap));
-    FRS_HIP(ctx->dec_next.ensure(sizeof(int32_t) * (size_t)cand_cap + 64));
-    if (!ctx->dec_count.ptr) {  // counters + the selection ticket: zeroed once, re-armed by the kernel
-        FRS_HIP(ctx->dec_count.ensure(64));
-        FRS_HIP(hipMemsetAsync(ctx->dec_count.ptr, 0, ctx->dec_count.bytes, st));
+    if (const int rc = stage_decode_tables(ctx, c, stream_off, fbase.data(), pcm_off, dmin, dmax, out_dtype, out_dev))
+        return rc;
+    if (const int rc = launch_selection(ctx, c)) return rc;
+    if (c.r.pipe_opt) {
+        bool done = false;
+        const int rc = decode_optimistic(ctx, c, &done);
+        if (rc || done) return rc;
     }
-    {
-        // a grown buffer may come back at the same address with stale words (possibly of the current epoch), and an
-        // epoch that wraps could match an old word: zero the status words in both cases
-        const size_t before = ctx->dec_status.bytes;
-        FRS_HIP(ctx->dec_status.ensure(sizeof(uint64_t) * (size_t)std::min<int64_t>(nblocks, kSelOnePassBlocks)));
-        bool wrap = false;
-        if (++ctx->dec_epoch >= (1u << 24)) {
-            ctx->dec_epoch = 1;
-            wrap = true;
-        }
-        if (ctx->dec_status.bytes != before || wrap)
-            FRS_HIP(hipMemsetAsync(ctx->dec_status.ptr, 0, ctx->dec_status.bytes, st));
-    }
-    // per-call tables through the context's pinned staging in one DMA copy: stream_off | fbase | pcm_off | the
-    // fused decode's per-stream (float32(max - min), float32(min)) pairs; the result counters come back after them
-    const size_t tab = sizeof(int64_t) * (size_t)(nstreams + 1);
-    const size_t dn_bytes = fused ? sizeof(float2) * (size_t)nstreams : 0;
-    FRS_HIP(ctx->dec_soff.ensure(3 * tab + dn_bytes + sizeof(int64_t) * frames + 64));
-    FRS_HIP(ctx->pin.ensure(3 * tab + dn_bytes + 128));
-    int64_t *htab = ctx->pin.at<int64_t>(0);
-    memcpy(htab, stream_off, tab);
-    memcpy(htab + (nstreams + 1), fbase.data(), tab);
-    memcpy(htab + 2 * (nstreams + 1), pcm_off, tab);
-    float2 *hdn = reinterpret_cast<float2 *>(htab + 3 * (nstreams + 1));
-    if (fused)  // python-float arithmetic first (data_max - data_min in double), then NEP 50 casts to float32
-        for (int s = 0; s < nstreams; s++) hdn[s] = make_float2((float)(dmax[s] - dmin[s]), (float)dmin[s]);
-    // one stream through the one-pass selection (a bbox query): the tables ride in the selection kernel's arguments
-    const bool tabs_by_arg = nstreams == 1 && nblocks <= kSelOnePassBlocks;
-    SmallTabs stabs = {};
-    if (tabs_by_arg) {
-        memcpy(stabs.v, htab, 3 * tab + dn_bytes);  // 6 int64 + one float2
-    } else {
-        FRS_HIP(hipMemcpyAsync(ctx->dec_soff.ptr, htab, 3 * tab + dn_bytes, hipMemcpyHostToDevice, st));
-    }
-    int64_t *dsoff = ctx->dec_soff.as<int64_t>();
-    int64_t *dfbase = dsoff + (nstreams + 1);
-    int64_t *dpoff = dfbase + (nstreams + 1);
-    const float2 *ddn = reinterpret_cast<const float2 *>(dpoff + (nstreams + 1));
-    int64_t *dchain = reinterpret_cast<int64_t *>(
-        (reinterpret_cast<uintptr_t>(dpoff + (nstreams + 1)) + dn_bytes + 7) & ~(uintptr_t)7);
-    int *ncand = ctx->dec_count.as<int>();
-    int *nvalid = ncand + 1;
-    int *bad = ncand + 2;
-    unsigned long long *ticket = reinterpret_cast<unsigned long long *>(ctx->dec_count.as<char>() + 16);
-    int64_t *cpos = ctx->dec_cand.as<int64_t>();
-    int64_t *ends = cpos + cand_cap;
-    int32_t *nexti = ctx->dec_next.as<int32_t>();
-    // multi-channel decodes of a large range (the two-pass selection): the span check from prefix CRCs the selection
-    // folds (k_span_pcrc), within the x^(8m) table range.  Measured (round 5, MI355X): a 4-band 16384^2 stream (one
-    // stream of 65536 32-KB frames: the lane span check has few, long spans) select + span 2.49 -> 1.94 ms; the C4
-    // batched mono decode (6241 streams of 8-KB frames) 2.16 -> 3.21 ms (the selection's CRC fold costs more than the
-    // reading span check it replaces: 1 LDS table lookup per byte either way, at lower occupancy), so mono keeps the
-    // reading form.  Round 6 (both counts in the queue form): select + span 1.73 (reading) vs 1.84 ms (prefix) on C4,
-    // the 4-band stream's decode 5.35 -> 4.91 ms.  FRS_SPAN_READ=1 / 2 forces the reading / prefix form (tests).
-    const char *span_env = nblocks > kSelOnePassBlocks ? getenv("FRS_SPAN_READ") : nullptr;  // (no env walk per query)
-    const int span_mode = span_env ? atoi(span_env) : 0;
-    const bool pcrc_span = span_mode != 1 && (span_mode == 2 || mcl) && nblocks > kSelOnePassBlocks &&
-                           (lane || !pipe) && max_frame < (int64_t)4096 * 256;
-    uint32_t *BPv = nullptr;
-    uint16_t *sbibv = nullptr, *pcrcv = nullptr;
-    hipEvent_t ev;
-    prof_begin(ctx, "decode", &ev);
-    if (nblocks <= kSelOnePassBlocks) {
-        if (sel_small)
-            k_sync_select<kSelStepsSmall><<<(unsigned)nblocks, kSelThreads, 0, st>>>(
-                blob_dev, blob_bytes, dsoff, nstreams, channels, bps, ctx->dec_status.as<uint64_t>(), ticket,
-                ctx->dec_epoch, nblocks, cpos, cand_cap, ncand, tabs_by_arg ? dsoff : nullptr, stabs);
-        else
-            k_sync_select<kSelSteps><<<(unsigned)nblocks, kSelThreads, 0, st>>>(
-                blob_dev, blob_bytes, dsoff, nstreams, channels, bps, ctx->dec_status.as<uint64_t>(), ticket,
-                ctx->dec_epoch, nblocks, cpos, cand_cap, ncand, tabs_by_arg ? dsoff : nullptr, stabs);
-    } else {
-        // (its own buffer: the one-pass status words must keep their epoch tags)
-        // [bcount int32 | bbase int64 | bpos: kSelBlkCap positions per block]
-        FRS_HIP(ctx->dec_sel.ensure(sizeof(int64_t) * (size_t)(2 * nblocks + 4 + (int64_t)kSelBlkCap * nblocks)));
-        int32_t *bcount = ctx->dec_sel.as<int32_t>();
-        int64_t *bbase = ctx->dec_sel.as<int64_t>() + (nblocks + 1) / 2 + 1;
-        int64_t *bpos = bbase + nblocks + 1;
-        // blocks whose 64 KB lie inside the range take the unguarded instance; the last, partial block its own launch
-        const int64_t nfull = std::min<int64_t>(nblocks, lead_bytes / kSelBytes);
-        if (pcrc_span) {
-            // [BP u32 (nblocks + 1) | bfirst u32 nblocks | bcrc u16 nblocks | bipc u16 32 nblocks | sbib u16 ns + 1 |
-            //  pcrc u16 cand_cap]
-            const size_t nb = (size_t)nblocks;
-            const size_t bytes = 4 * (nb + 1) + 4 * nb + 2 * nb + 2 * kSelBlkCap * nb + 2 * ((size_t)nstreams + 1) +
-                                 2 * (size_t)cand_cap + 64;
-            FRS_HIP(ctx->dec_crc.ensure(bytes));
-            BPv = ctx->dec_crc.as<uint32_t>();
-            uint32_t *bfirst = BPv + nb + 1;
-            uint16_t *bcrc = reinterpret_cast<uint16_t *>(bfirst + nb);
-            uint16_t *bipc = bcrc + nb;
-            sbibv = bipc + kSelBlkCap * nb;
-            pcrcv = sbibv + nstreams + 1;
-            const int lead = (int)(reinterpret_cast<uintptr_t>(blob_dev) & 15);
-            FRS_HIP(hipMemsetAsync(bfirst, 0xFF, 4 * nb, st));
-            k_bound_mark<<<(unsigned)((nstreams + 255) / 256), 256, 0, st>>>(dsoff, nstreams, lead, bfirst);
-            if (nfull)
-                k_sync_count<true, true><<<(unsigned)nfull, kSelThreads, 0, st>>>(
-                    blob_dev, blob_bytes, dsoff, nstreams, channels, bps, bcount, bpos, bcrc, bipc, bfirst, sbibv, 0);
-            if (nblocks > nfull)
-                k_sync_count<true, false><<<(unsigned)(nblocks - nfull), kSelThreads, 0, st>>>(
-                    blob_dev, blob_bytes, dsoff, nstreams, channels, bps, bcount, bpos, bcrc, bipc, bfirst, sbibv, nfull);
-            k_sync_scan<<<1, 1024, 0, st>>>(bcount, bbase, nblocks, ncand, bcrc, BPv);
-            k_sync_scatter<true><<<(unsigned)nblocks, kSelThreads, 0, st>>>(blob_dev, blob_bytes, dsoff, nstreams,
-                                                                            channels, bps, bbase, cpos, cand_cap,
-                                                                            bcount, bpos, pcrcv, BPv, bipc);
-        } else {
-            if (nfull)
-                k_sync_count<false, true><<<(unsigned)nfull, kSelThreads, 0, st>>>(
-                    blob_dev, blob_bytes, dsoff, nstreams, channels, bps, bcount, bpos, nullptr, nullptr, nullptr,
-                    nullptr, 0);
-            if (nblocks > nfull)
-                k_sync_count<false, false><<<(unsigned)(nblocks - nfull), kSelThreads, 0, st>>>(
-                    blob_dev, blob_bytes, dsoff, nstreams, channels, bps, bcount, bpos, nullptr, nullptr, nullptr,
-                    nullptr, nfull);
-            k_sync_scan<<<1, 1024, 0, st>>>(bcount, bbase, nblocks, ncand);
-            k_sync_scatter<<<(unsigned)nblocks, kSelThreads, 0, st>>>(blob_dev, blob_bytes, dsoff, nstreams, channels,
-                                                                      bps, bbase, cpos, cand_cap, bcount, bpos);
-        }
-    }
-    prof_end(ctx, "decode", ev);
-    DecOut dout;
-    dout.out = out_dev;
-    dout.dn = ddn;
-    dout.dtype = out_dtype;
-    dout.shift = bps > 16 ? 16 : 0;
-    int *hv = reinterpret_cast<int *>(reinterpret_cast<char *>(htab) + ((3 * tab + dn_bytes + 15) & ~(size_t)15));
-    // small mono ranges (C5 queries): the optimistic pipe decode first (no span check, no chain); only when it
-    // declined (counts[6]: a false sync, a frame for the one-lane decoder) do the span check, chain and decode below
-    // run, after one more host round trip.  FRS_PIPE_OPT=0 at context creation disables it (tests)
-    const bool pipe_opt = pipe && !lane && max_frame < (int64_t)4096 * 256 && ctx->pipe_opt;
-    if (pipe_opt) {
-        // the last work-group copies the counters into hv (page-locked) itself: no device-to-host copy to wait for
-        hv[6] = -1;
-        prof_begin(ctx, "decode_frames", &ev);
-        k_decode_frames_pipe<true><<<(unsigned)frames, 192, 0, st>>>(blob_dev, dsoff, nstreams, dpoff, cpos, ends,
-                                                                     dfbase, dchain, frames, channels, bps, pcm_dev,
-                                                                     blocksize, nvalid, dout, ncand, ncand, hv);
-        prof_end(ctx, "decode_frames", ev);
-        FRS_HIP(hipGetLastError());
-        // completion = the last work-group's page-locked counters (hv[6] written last, after system-scope fences over
-        // every work-group's output): polled here, a few microseconds before the stream's completion signal; bounded,
-        // then the stream synchronisation decides.  FRS_C5_POLL=0: synchronise only
-        static const bool poll = !(getenv("FRS_C5_POLL") && atoi(getenv("FRS_C5_POLL")) == 0);
-        bool seen = false;
-        if (poll && !ctx->prof) {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (uint32_t k = 0;; k++) {
-                if (__atomic_load_n(&hv[6], __ATOMIC_ACQUIRE) != -1) {
-                    seen = true;
-                    break;
-                }
-                if ((k & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-            }
-        }
-        if (!seen) FRS_HIP(hipStreamSynchronize(st));
-        if (__atomic_load_n(&hv[6], __ATOMIC_ACQUIRE) == -1) {  // (not expected) the epilogue did not run: copy, re-arm
-            FRS_HIP(hipMemcpyAsync(hv, ncand, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-            FRS_HIP(hipMemsetAsync(ncand + 8, 0, sizeof(int), st));
-            FRS_HIP(hipStreamSynchronize(st));
-            if (hv[6] == 0) hv[6] = 1;  // decide by the full path
-        }
-        if (hv[6] == 0) {
-            // the early completion covers output in page-locked host memory (the kernels' system-scope fences); a
-            // device-memory output is complete in the stream's order only: synchronise for it
-            if (seen) {
-                if (out_dev && ctx->is_host_alloc(out_dev, 1)) ctx->unsynced = true;
-                else FRS_HIP(hipStreamSynchronize(st));
-            }
-            prof_collect(ctx);
-            if (hv[7] != frames) {
-                ctx->err = "decoded " + std::to_string(hv[7]) + " valid frames, expected " + std::to_string(frames);
-                return FRS_E_CORRUPT;
-            }
-            return FRS_OK;
-        }
-    }
-    prof_begin(ctx, "decode_span", &ev);
-    // launched before the host knows the candidate count (no mid-query sync): an upper-bound grid strides over
-    // *ncand on the device; an overflowing selection makes every later kernel a no-op and is reported below
-    if (pcrc_span) {
-        k_span_pcrc<<<(unsigned)((std::min<int64_t>(cand_cap, 2 * frames + 256) + 255) / 256), 256, 0, st>>>(
-            dsoff, nstreams, cpos, ncand, (int)cand_cap, max_frame, pcrcv, BPv, sbibv,
-            (int)(reinterpret_cast<uintptr_t>(blob_dev) & 15), ends, nexti);
-    } else if (lane || !pipe) {  // batched (or long multi-channel / 32-bit frames, which the wave form would walk on
-                                 // one lane past its LDS stage): one lane per candidate, over an upper-bound grid
-        k_span_crc_lane<<<(unsigned)((std::min<int64_t>(cand_cap, 2 * frames + 256) + 255) / 256), 256, 0, st>>>(
-            blob_dev, dsoff, nstreams, cpos, ncand, (int)cand_cap, max_frame, ends, nexti);
-    } else if (max_frame < (int64_t)4096 * 256) {  // x^(8m) table range of the wave CRC
-        const int64_t grid = std::min<int64_t>(cand_cap, std::min<int64_t>(2 * frames + 256, (int64_t)ctx->num_cus * 64));
-        k_span_crc_wave<<<(unsigned)grid, 64, 0, st>>>(blob_dev, dsoff, nstreams, cpos, ncand, (int)cand_cap,
-                                                       max_frame, ends, nexti);
-    } else {
-        k_span_crc<<<(unsigned)((cand_cap + 63) / 64), 64, 0, st>>>(blob_dev, dsoff, nstreams, cpos, ncand,
-                                                                    (int)cand_cap, max_frame, ends, nexti);
-    }
-    k_chain_lds<<<nstreams, nstreams == 1 ? 1024 : 64, 0, st>>>(dsoff, nstreams, cpos, ncand, (int)cand_cap, nexti,
-                                                                 dfbase, dchain, bad);
-    prof_end(ctx, "decode_span", ev);
-    prof_begin(ctx, pipe_opt ? "decode_fallback" : "decode_frames", &ev);
-    if (lane) {
-        FRS_HIP(ctx->dec_fb.ensure(sizeof(int32_t) * (size_t)frames + 64));
-        int32_t *fbl = ctx->dec_fb.as<int32_t>();
-        int *fbc = ncand + 3;
-        const unsigned lg = (unsigned)((frames + 255) / 256);
-        // (experiment) FRS_DEC_LANE_LDS: dynamic LDS per work-group, i.e. a cap on the lane decoder's occupancy
-        static const size_t lane_lds = getenv("FRS_DEC_LANE_LDS") ? (size_t)atol(getenv("FRS_DEC_LANE_LDS")) : 0;
-        const int okind = !fused ? kOutPcm : out_dtype == FRS_DT_I16 ? kOutI16 : out_dtype == FRS_DT_U16 ? kOutU16
-                                   : out_dtype == FRS_DT_U8 ? kOutU8 : kOutAny;
-#define FRS_LANE(K) k_decode_frames_lane<K><<<lg, 256, lane_lds, st>>>(blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase, \
-                                                              dchain, frames, bps, pcm_dev, blocksize, nvalid, dout, fbl, fbc)
-        switch (okind) {
-        case kOutPcm: FRS_LANE(kOutPcm); break;
-        case kOutI16: FRS_LANE(kOutI16); break;
-        case kOutU16: FRS_LANE(kOutU16); break;
-        case kOutU8: FRS_LANE(kOutU8); break;
-        default: FRS_LANE(kOutAny); break;
-        }
-#undef FRS_LANE
-        k_decode_frames_wave_list<<<(unsigned)std::min<int64_t>(frames, 4 * (int64_t)ctx->num_cus), 64, 0, st>>>(
-            blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase, dchain, channels, bps, pcm_dev, blocksize, nvalid,
-            dout, fbl, fbc);
-    } else if (mcl) {
-        FRS_HIP(ctx->dec_fb.ensure(sizeof(int32_t) * (size_t)frames + 64));
-        int32_t *fbl = ctx->dec_fb.as<int32_t>();
-        int *fbc = ncand + 3;
-        int32_t *planar = ctx->dec_pcm.as<int32_t>();
-        int8_t *fchass = nullptr;
-        if (channels == 2) {
-            FRS_HIP(ctx->dec_chass.ensure((size_t)frames + 64));
-            fchass = ctx->dec_chass.as<int8_t>();
-        }
-        const int planar16 = channels >= 3;  // independent channels of <= 16 bits (two: the side is 17 bits)
-        if (planar16)
-            k_decode_frames_lane<kOutPlanar16, true><<<(unsigned)((frames + 255) / 256), 256, 0, st>>>(
-                blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase, dchain, frames, bps, pcm_dev, blocksize, nvalid,
-                dout, fbl, fbc, channels, planar, fchass);
-        else
-            k_decode_frames_lane<kOutPcm, true><<<(unsigned)((frames + 255) / 256), 256, 0, st>>>(
-                blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase, dchain, frames, bps, pcm_dev, blocksize, nvalid,
-                dout, fbl, fbc, channels, planar, fchass);
-        const int cpf = (blocksize + 255) / 256;
-        k_interleave_dn<<<(unsigned)(frames * cpf), 256, 0, st>>>(planar, dpoff, dfbase, nstreams, channels, blocksize,
-                                                                 pcm_dev, dout, fchass, cpf, planar16);
-        k_decode_frames_wave_list<<<(unsigned)std::min<int64_t>(frames, 4 * (int64_t)ctx->num_cus), 64, 0, st>>>(
-            blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase, dchain, channels, bps, pcm_dev, blocksize, nvalid,
-            dout, fbl, fbc);
-    } else if (pipe) {
-        k_decode_frames_pipe<<<(unsigned)frames, 192, 0, st>>>(blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase,
-                                                               dchain, frames, channels, bps, pcm_dev, blocksize, nvalid,
-                                                               dout);
-    } else
-        k_decode_frames_wave<<<(unsigned)frames, 64, 0, st>>>(blob_dev, dsoff, nstreams, dpoff, cpos, ends, dfbase,
-                                                              dchain, frames, channels, bps, pcm_dev, blocksize, nvalid,
-                                                              dout);
-    prof_end(ctx, pipe_opt ? "decode_fallback" : "decode_frames", ev);
-    FRS_HIP(hipGetLastError());
-    FRS_HIP(hipMemcpyAsync(hv, ncand, sizeof(int) * 8, hipMemcpyDeviceToHost, st));
-    FRS_HIP(hipStreamSynchronize(st));
-    prof_collect(ctx);
-    if (ctx->prof && (lane || mcl)) {  // frames the lane decoder handed to the wave decoder (profile_avg_ms of this name)
-        ProfEntry &e = ctx->prof_tab["lane_fallback_frames"];
-        e.total_ms += hv[3];
-        e.count += 1;
-    }
-    if ((int64_t)hv[0] > cand_cap) {
-        ctx->err = "too many frame sync candidates (" + std::to_string(hv[0]) + " > " + std::to_string(cand_cap) +
-                   "): not a FLAC stream of the expected layout";
-        return FRS_E_CORRUPT;
-    }
-    const int valid = hv[1];
-    if (hv[2] != 0 || valid != frames) {
-        ctx->err = "decoded " + std::to_string(valid) + " valid frames, expected " + std::to_string(frames) +
-                   (hv[2] ? " (broken frame chain)" : "");
-        return FRS_E_CORRUPT;
-    }
-    return FRS_OK;
+    if (const int rc = launch_span_and_chain(ctx, c)) return rc;
+    if (const int rc = launch_frame_decoders(ctx, c)) return rc;
+    return finish_decode(ctx, c);
 }
 
 int denormalize_job(frs_ctx *ctx, const int32_t *pcm_dev, int64_t n, int pcm_bps, double dmin, double dmax,

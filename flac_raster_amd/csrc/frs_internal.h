@@ -31,6 +31,7 @@ struct DevBuf {
         bytes = 0;
     }
     template <typename T> T *as() const { return reinterpret_cast<T *>(ptr); }
+    template <typename T> T *at(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(ptr) + off); }
 };
 
 // pinned host staging (small per-call H2D tables and the packed D2H results of the fast encode path): one
