@@ -39,7 +39,13 @@ EXPORTS = (
     "frs_profile_reset", "frs_comm_unique_id", "frs_comm_init", "frs_comm_destroy", "frs_comm_allgather_i64",
     "frs_compare_device", "frs_compare",
     "frs_place_tiles_device", "frs_decode_tiles_window_device", "frs_decode_tiles_window",
+    "frs_downsample2_device", "frs_downsample2",
 )
+
+# enum frs_resample
+RESAMPLE_NEAREST = 0
+RESAMPLE_AVERAGE = 1
+RESAMPLE_CODES = {"nearest": RESAMPLE_NEAREST, "average": RESAMPLE_AVERAGE}
 
 # launch constants of k_compare (csrc/frs_compare.hip: kCmpBlock, kCmpUnroll, kCmpMaxGroups): a work-group step covers
 # COMPARE_BLOCK * COMPARE_UNROLL 16-byte vectors of each raster, and a band gets one work-group per step up to
@@ -231,6 +237,11 @@ def load_library(path: Optional[os.PathLike] = None):
         L.frs_decode_tiles_window_device.argtypes = decw_args
         L.frs_decode_tiles_window.restype = i32
         L.frs_decode_tiles_window.argtypes = decw_args
+        ds_args = [ctxp, rdp, vp, rdp, vp, i32]
+        L.frs_downsample2_device.restype = i32
+        L.frs_downsample2_device.argtypes = ds_args
+        L.frs_downsample2.restype = i32
+        L.frs_downsample2.argtypes = ds_args
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -676,6 +687,44 @@ class Context:
         win, n, soff, soff_p, mn, mn_p, mx, mx_p = self._window_args(stream_off, windows, data_min, data_max)
         self._check(self.lib.frs_decode_tiles_window(self.handle, _p(b), soff_p, n, int(bps), int(blocksize), win, mn_p,
                                                      mx_p, ctypes.byref(d), _p(out)))
+        return out
+
+    # ---- pyramid
+    @staticmethod
+    def _resample_code(mode) -> int:
+        if isinstance(mode, str):
+            if mode not in RESAMPLE_CODES:
+                raise ValueError(f"resampling must be one of {sorted(RESAMPLE_CODES)}, got {mode!r}")
+            return RESAMPLE_CODES[mode]
+        return int(mode)
+
+    def downsample2_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, dst_desc: Optional[RasterDesc] = None,
+                           mode="average") -> RasterDesc:
+        """frs_downsample2_device: one 2x step from the device raster at src_ptr (laid out as src_desc) to the one at
+        dst_ptr.  dst_desc defaults to the dense ceil(height/2) x ceil(width/2) raster.  `mode` is "average", "nearest"
+        or an enum frs_resample value.  Returns the destination descriptor."""
+        if dst_desc is None:
+            dst_desc = RasterDesc()
+            dst_desc.height, dst_desc.width = (src_desc.height + 1) // 2, (src_desc.width + 1) // 2
+            dst_desc.row_stride, dst_desc.band_stride = dst_desc.width, dst_desc.width * dst_desc.height
+            dst_desc.dtype, dst_desc.nbands = src_desc.dtype, src_desc.nbands
+        self._check(self.lib.frs_downsample2_device(self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr),
+                                                    ctypes.byref(dst_desc), ctypes.c_void_p(dst_ptr),
+                                                    self._resample_code(mode)))
+        return dst_desc
+
+    def downsample2_host(self, src: np.ndarray, mode="average") -> np.ndarray:
+        """frs_downsample2 on a host raster ((bands, h, w) or (h, w)): the reduced raster, same rank and dtype."""
+        a = np.ascontiguousarray(src)
+        if a.ndim not in (2, 3) or a.dtype not in DTYPE_CODES or a.size == 0:
+            raise ValueError("downsample2_host needs a non-empty (bands, h, w) or (h, w) array of a raster dtype")
+        nb = a.shape[0] if a.ndim == 3 else 1
+        h, w = a.shape[-2], a.shape[-1]
+        sd = self.make_raster_desc(h, w, a.dtype, nbands=nb)
+        dd = self.make_raster_desc((h + 1) // 2, (w + 1) // 2, a.dtype, nbands=nb)
+        out = np.zeros(((nb,) if a.ndim == 3 else ()) + (dd.height, dd.width), dtype=a.dtype)
+        self._check(self.lib.frs_downsample2(self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out),
+                                             self._resample_code(mode)))
         return out
 
     # ---- bench helpers

@@ -95,12 +95,28 @@ def create_streaming(
     verify: bool = typer.Option(False, "--verify", help="Extension: read the written file back, decode it into one "
                                                         "raster on the GPU and compare it with band 1 of the source "
                                                         "there (single GPU only); exit status 3 when it differs"),
+    overviews: bool = typer.Option(False, "--overviews", help="Extension: append reduced-resolution levels (each a 2x "
+                                                              "reduction of the one before, made on the GPU) until "
+                                                              "one fits in a single tile (single GPU only)"),
+    resampling: str = typer.Option("average", "--resampling", help="Overview resampling: average or nearest"),
+    overview_levels: Optional[int] = typer.Option(None, "--overview-levels", min=0,
+                                                  help="Write at most N overview levels"),
 ):
     """Create Netflix-style streaming FLAC with self-contained tiles"""
     from . import streaming
-    # --verify is checked before anything else is looked at or done
+    # --verify and --overviews are checked before anything else is looked at or done
     if verify and (gpus > 1 or distributed):
         typer.echo("Error: --verify runs on one GPU: it cannot be combined with --gpus > 1 or --distributed", err=True)
+        raise typer.Exit(1)
+    if overviews and (gpus > 1 or distributed):
+        typer.echo("Error: --overviews runs on one GPU: it cannot be combined with --gpus > 1 or --distributed",
+                   err=True)
+        raise typer.Exit(1)
+    if resampling not in streaming.RESAMPLING:
+        typer.echo(f"Error: --resampling must be one of {', '.join(streaming.RESAMPLING)}, got: {resampling}", err=True)
+        raise typer.Exit(1)
+    if not overviews and (resampling != "average" or overview_levels is not None):
+        typer.echo("Error: --resampling and --overview-levels need --overviews", err=True)
         raise typer.Exit(1)
     if not input_file.exists():
         typer.echo(f"Error: Input file does not exist: {input_file}", err=True)
@@ -129,8 +145,13 @@ def create_streaming(
             from .distributed import create_streaming_distributed
             index = create_streaming_distributed(input_file, output_file, tile_size)
         else:
-            index = streaming.create_streaming(input_file, output_file, tile_size)
-        typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles)")
+            index = streaming.create_streaming(input_file, output_file, tile_size, overviews=overviews,
+                                               resampling=resampling, max_levels=overview_levels)
+        top = max(streaming.overview_levels(index))
+        if overviews:
+            typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles, {top} overview levels)")
+        else:
+            typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles)")
         if verify:
             from . import geotiff
             ex = streaming.verify_streaming(output_file, geotiff.read(input_file).data[0])
@@ -138,6 +159,8 @@ def create_streaming(
             if differs:
                 typer.echo(f"VERIFY: differs (n_different={ex['n_different']}, "
                            f"max_difference={ex['max_difference']})")
+            elif overviews:
+                typer.echo(f"VERIFY: lossless (levels 0..{ex['levels_checked'] - 1})")
             else:
                 typer.echo("VERIFY: lossless")
     except Exception as e:
@@ -158,12 +181,23 @@ def extract_streaming(
     last: bool = typer.Option(False, "--last", help="Extract last tile"),
     mosaic: bool = typer.Option(False, "--mosaic", help="Extension: mosaic every tile intersecting --bbox"),
     all_tiles: bool = typer.Option(False, "--all", help="Extension: decode every tile and write the whole raster"),
+    level: Optional[int] = typer.Option(None, "--level", min=0, help="Extension: read overview level K (0: full "
+                                                                     "resolution) of a file written with --overviews"),
+    max_size: Optional[int] = typer.Option(None, "--max-size", min=1,
+                                           help="Extension: with --all or --bbox --mosaic, read the finest level at "
+                                                "which the result is at most N pixels on its longer side"),
 ):
     """Extract tiles from Netflix-style streaming FLAC files"""
     from . import streaming
     # --all takes no tile selection: checked before anything is read
     if all_tiles and (bbox is not None or tile_id is not None or center or last):
         typer.echo("Error: --all cannot be combined with --bbox, --tile-id, --center or --last", err=True)
+        raise typer.Exit(1)
+    if level is not None and max_size is not None:
+        typer.echo("Error: --level and --max-size exclude each other", err=True)
+        raise typer.Exit(1)
+    if max_size is not None and not (all_tiles or (mosaic and bbox is not None)):
+        typer.echo("Error: --max-size works with --all or --bbox --mosaic only", err=True)
         raise typer.Exit(1)
     coords = None
     if bbox:
@@ -175,20 +209,33 @@ def extract_streaming(
             typer.echo(f"Error: Invalid bbox format. Use 'xmin,ymin,xmax,ymax': {e}", err=True)
             raise typer.Exit(1)
     try:
+        lvl = level or 0
+        if max_size is not None:
+            _, index = streaming.read_index(flac_url)
+            wpx, hpx = int(index["width"]), int(index["height"])
+            if not all_tiles:
+                from . import geotiff
+                t = geotiff.Affine(*index["transform"][:6])
+                if t.b == 0 and t.d == 0:
+                    win = streaming.bbox_pixel_window(t, coords, wpx, hpx)
+                    wpx, hpx = max(win["width"], 1), max(win["height"], 1)
+            lvl = streaming.pick_level(index, wpx, hpx, max_size)
+        at = f" (level {lvl})" if level is not None or max_size is not None else ""
         if all_tiles:
-            index = streaming.extract_all(flac_url, output)
-            typer.echo(f"SUCCESS: Extracted all {len(index['frames'])} tiles to {output}")
+            index = streaming.extract_all(flac_url, output, level=lvl)
+            typer.echo(f"SUCCESS: Extracted all {len(index['frames'])} tiles to {output}{at}")
         elif mosaic and coords is not None:
             from . import geotiff
-            arr, win, tr = streaming.extract_bbox_mosaic(flac_url, coords)
+            arr, win, tr = streaming.extract_bbox_mosaic(flac_url, coords, level=lvl)
             n, index = streaming.read_index(flac_url)
             crs = index.get("crs")
             epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
             geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
-            typer.echo(f"SUCCESS: mosaic {win} -> {output}")
+            typer.echo(f"SUCCESS: mosaic {win} -> {output}{at}")
         else:
-            f = streaming.extract_streaming(flac_url, output, bbox=coords, tile_id=tile_id, center=center, last=last)
-            typer.echo(f"SUCCESS: Extracted tile {f['frame_id']} to {output}")
+            f = streaming.extract_streaming(flac_url, output, bbox=coords, tile_id=tile_id, center=center, last=last,
+                                            level=lvl)
+            typer.echo(f"SUCCESS: Extracted tile {f['frame_id']} to {output}{at}")
     except (KeyError, LookupError, ValueError) as e:
         typer.echo(f"Error: {e}", err=True)
         raise typer.Exit(1)

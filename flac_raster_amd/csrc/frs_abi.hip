@@ -774,3 +774,93 @@ int frs_decode_tiles_window(frs_ctx *ctx, const uint8_t *blob_host, const int64_
 }
 
 }  // extern "C"
+
+// argument checks of the pyramid step (frs_downsample2*), before anything is sized, copied or launched
+static int check_downsample_desc(frs_ctx *ctx, const frs_raster_desc *d) {
+    if (!d) { ctx->err = "null desc"; return FRS_E_ARG; }
+    if (d->height < 1 || d->width < 1) { ctx->err = "downsample: height and width must be >= 1"; return FRS_E_ARG; }
+    if (d->row_stride < d->width) { ctx->err = "row_stride < width"; return FRS_E_ARG; }
+    if (d->nbands < 1 || d->nbands > frs::kMaxChannels) { ctx->err = "nbands must be 1..8"; return FRS_E_ARG; }
+    if (frs::dtype_size(d->dtype) == 0) { ctx->err = "bad dtype"; return FRS_E_ARG; }
+    if (compare_extent(d->height, d->width, d->nbands, d->row_stride, d->nbands > 1 ? d->band_stride : 0) < 0) {
+        ctx->err = "downsample: raster extent overflows";
+        return FRS_E_ARG;
+    }
+    if (d->nbands > 1 && d->band_stride < (d->height - 1) * d->row_stride + d->width) {
+        ctx->err = "band_stride too small";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
+static int check_downsample_args(frs_ctx *ctx, const frs_raster_desc *src, const frs_raster_desc *dst, int32_t mode) {
+    if (int rc = check_downsample_desc(ctx, src)) return rc;
+    if (int rc = check_downsample_desc(ctx, dst)) return rc;
+    if (src->dtype != dst->dtype || src->nbands != dst->nbands) {
+        ctx->err = "downsample: source and destination differ in dtype or nbands";
+        return FRS_E_ARG;
+    }
+    if (dst->height != (src->height + 1) / 2 || dst->width != (src->width + 1) / 2) {
+        ctx->err = "downsample: the destination must be ceil(height/2) x ceil(width/2) of the source";
+        return FRS_E_ARG;
+    }
+    if (mode != FRS_RESAMPLE_NEAREST && mode != FRS_RESAMPLE_AVERAGE) { ctx->err = "downsample: bad mode"; return FRS_E_ARG; }
+    return FRS_OK;
+}
+
+// bytes from a raster's origin to the end of its last row (the descriptor is already validated)
+static size_t raster_bytes(const frs_raster_desc *d) {
+    return (size_t)compare_extent(d->height, d->width, d->nbands, d->row_stride, d->nbands > 1 ? d->band_stride : 0) *
+           (size_t)frs::dtype_size(d->dtype);
+}
+
+extern "C" {
+
+int frs_downsample2_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev, const frs_raster_desc *dst,
+                           void *dst_dev, int32_t mode) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
+    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src_dev), b = reinterpret_cast<uintptr_t>(dst_dev);
+    if (!src_dev || !dst_dev || a % es || b % es) {
+        ctx->err = "downsample: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    if (a < b + raster_bytes(dst) && b < a + raster_bytes(src)) {
+        ctx->err = "downsample: source and destination overlap";
+        return FRS_E_ARG;
+    }
+    FRS_HIP(hipSetDevice(ctx->device));
+    return frs::downsample_job(ctx, src, src_dev, dst, dst_dev, mode);
+}
+
+int frs_downsample2(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
+                    void *dst_host, int32_t mode) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
+    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src_host), b = reinterpret_cast<uintptr_t>(dst_host);
+    if (!src_host || !dst_host || a % es || b % es) {
+        ctx->err = "downsample: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    const size_t sbytes = raster_bytes(src), dbytes = raster_bytes(dst);
+    if (a < b + dbytes && b < a + sbytes) {
+        ctx->err = "downsample: source and destination overlap";
+        return FRS_E_ARG;
+    }
+    FRS_HIP(hipSetDevice(ctx->device));
+    FRS_HIP(ctx->raster_stage.ensure(sbytes));
+    FRS_HIP(ctx->arena_stage.ensure(dbytes));
+    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
+    // the destination goes up first: its row and band padding comes back as it was
+    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = frs::downsample_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, mode)) return rc;
+    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    return FRS_OK;
+}
+
+}  // extern "C"

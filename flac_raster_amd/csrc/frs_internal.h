@@ -177,4 +177,7 @@ int compare_job(frs_ctx *ctx, const frs_compare_desc *d, const void *a_dev, cons
 // Place ntiles decoded tiles into a device raster (frs_place.hip); the arguments are already validated.
 int place_job(frs_ctx *ctx, const frs_raster_desc *d, const void *tiles_dev, const int64_t *pcm_off,
               const frs_tile_window *win, int32_t ntiles, void *dst_dev);
+// One 2x reduction step between two device rasters (frs_pyramid.hip); the arguments are already validated.
+int downsample_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d, void *dst_dev,
+                   int32_t mode);
 }  // namespace frs

@@ -9,6 +9,18 @@ Differences from the reference are only in *how*: all tiles are encoded in one G
 loops tiles serially through two temporary files each), and extraction decodes any number of tiles in
 one batched GPU call.  ``extract_bbox_mosaic`` is an extension: the reference returns
 only the first intersecting tile.
+
+Overviews (extension, ``create_streaming*(overviews=True)``): reduced-resolution levels of band 1, each a 2x
+reduction of the one before (frs_downsample2_device), tiled and encoded exactly as a raster of its own would be.
+Their tiles follow level 0's in the file -- ``[u32 index length][index][level-0 tiles][level-1 tiles]...`` -- and
+the index gains one key after ``frames``::
+
+    "overviews": {"resampling": "average", "levels": [
+        {"level": 1, "factor": 2, "width": w, "height": h, "transform": [...], "frames": [...]}, ...]}
+
+Everything a reader without overview support looks at (the top-level keys, ``frames``) is what it is without them.
+``level_index`` turns a level into a dict of the top-level index's shape, on which the selection and decode
+functions work unchanged.
 """
 from __future__ import annotations
 
@@ -49,6 +61,64 @@ def tile_transform_and_bbox(transform: geotiff.Affine, col: int, row: int, w: in
     xmax = xmin + (w * tt.a)
     ymin = ymax + (h * tt.e)
     return tt, [xmin, ymin, xmax, ymax]
+
+
+RESAMPLING = ("average", "nearest")
+
+
+def overview_shapes(height: int, width: int, tile_size: int, max_levels: Optional[int] = None) -> List[Tuple[int, int]]:
+    """(height, width) of overview levels 1, 2, ...: each level halves the one before with ceil, as long as the one
+    before does not fit in one tile; the last level does.  At most `max_levels` levels.  Pure host code."""
+    h, w, t = int(height), int(width), int(tile_size)
+    if h < 1 or w < 1 or t < 1:
+        raise ValueError("height, width and tile_size must be >= 1")
+    if max_levels is not None and max_levels < 0:
+        raise ValueError("max_levels must be >= 0")
+    out: List[Tuple[int, int]] = []
+    while max(h, w) > t and (max_levels is None or len(out) < max_levels):
+        h, w = (h + 1) // 2, (w + 1) // 2
+        out.append((h, w))
+    return out
+
+
+def level_transform(transform: Sequence[float], level: int) -> List[float]:
+    """The affine transform of overview level `level`: pixel sizes times 2**level, the origin unchanged (a level's
+    pixel (0, 0) starts where level 0's does).  The products are exact (a power of two)."""
+    a, b, c, d, e, f0 = (float(v) for v in list(transform)[:6])
+    f = float(2 ** int(level))
+    return [a * f, b * f, c, d * f, e * f, f0]
+
+
+def overview_levels(index: Dict) -> List[int]:
+    """The levels a streaming index holds: 0 and its overview levels."""
+    ov = index.get("overviews") or {}
+    return [0] + [int(lv["level"]) for lv in ov.get("levels", [])]
+
+
+def level_index(index: Dict, level: int = 0) -> Dict:
+    """A dict of the streaming index's own shape (crs, transform, width, height, tile_size, frames) for one level;
+    level 0 is the index itself.  select_frame, intersecting, first_intersecting, tile_windows and decode_into_window
+    work on the result unchanged.  LookupError (naming the levels present) for a level the file does not hold."""
+    if int(level) == 0:
+        return index
+    for lv in (index.get("overviews") or {}).get("levels", []):
+        if int(lv["level"]) == int(level):
+            return {"crs": index.get("crs"), "transform": list(lv["transform"]), "width": lv["width"],
+                    "height": lv["height"], "tile_size": index.get("tile_size"), "frames": lv["frames"]}
+    raise LookupError(f"level {level} not in this file (levels present: {overview_levels(index)})")
+
+
+def pick_level(index: Dict, width_px: int, height_px: int, max_size: int) -> int:
+    """The finest level at which a window of width_px x height_px level-0 pixels is at most `max_size` pixels on its
+    longer side (a level-k window has ceil(n / 2**k) pixels); the coarsest level when none qualifies.  Pure."""
+    if max_size < 1:
+        raise ValueError("max_size must be >= 1")
+    levels = sorted(overview_levels(index))
+    longer = max(int(width_px), int(height_px))
+    for k in levels:
+        if -(-longer // (1 << k)) <= max_size:
+            return k
+    return levels[-1]
 
 
 def tile_tags(crs: Optional[str], tt: geotiff.Affine, w: int, h: int, dtype, tmin: float, tmax: float):
@@ -226,12 +296,110 @@ def write_tiles(fd: int, offset: int, headers: Sequence[bytes], enc: EncodedTile
         list(ex.map(lambda t: run(bounds[t], bounds[t + 1]), range(k)))
 
 
+def encode_band_tiles_device(ctx: Context, raster_ptr: int, height: int, width: int, dtype, tile_size: int,
+                             arena, pinned: bool = False) -> EncodedTiles:
+    """encode_band_tiles for a dense band already in device memory: frs_encode_tiles_device into the device arena
+    `arena` (at least the descriptor's arena bound), the frames brought back to the host."""
+    _, bps = audio_params(1, min(tile_size, height), dtype)
+    d = ctx.make_desc(height, width, dtype, nbands=1, tile_h=tile_size, tile_w=tile_size, sample_rate=44100,
+                      bits_per_sample=bps)
+    off, mn, mx, sbps = ctx.encode_tiles_device(raster_ptr, d, arena)
+    n = int(off[-1])
+    frames = ctx.pinned(n) if pinned and n else np.empty(n, dtype=np.uint8)
+    if n:
+        arena.download(n, 0, out=frames)
+    return EncodedTiles(tile_grid(height, width, tile_size), frames, off, mn, mx, sbps)
+
+
+def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs: Optional[str], output: Path,
+                                tile_size: int, ctx: Optional[Context], tm: Dict[str, float], resampling: str,
+                                max_levels: Optional[int]) -> Dict:
+    """create_streaming_array(overviews=True): the band goes up once; level k is made from level k - 1 on the device
+    (frs_downsample2_device) and encoded there like a raster of its own.  Device memory held at any time: the band,
+    two level buffers and one arena (sized for level 0, the largest)."""
+    if resampling not in RESAMPLING:
+        raise ValueError(f"resampling must be one of {RESAMPLING}, got {resampling!r}")
+    ctx = ctx or default_context()
+    t0 = time.perf_counter()
+    H, W = band.shape
+    dtype = band.dtype
+    shapes = [(H, W)] + overview_shapes(H, W, tile_size, max_levels)
+    _, bps0 = audio_params(1, min(tile_size, H), dtype)
+    d0 = ctx.make_desc(H, W, dtype, nbands=1, tile_h=tile_size, tile_w=tile_size, sample_rate=44100,
+                       bits_per_sample=bps0)
+    bufs = [ctx.alloc(band.nbytes)]
+    pyr_s = 0.0
+    encs: List[EncodedTiles] = []
+    try:
+        bufs[0].upload(band)
+        arena = ctx.alloc(ctx.arena_bound(d0))
+        bufs.append(arena)
+        # level k lives in lv[k % 2] (level 1 and 2 get a buffer each, level k + 2 fits in level k's)
+        lv = [ctx.alloc(h * w * dtype.itemsize) for h, w in shapes[1:3]]
+        bufs.extend(lv)
+        cur, cur_desc = bufs[0], ctx.make_raster_desc(H, W, dtype)
+        for k, (h, w) in enumerate(shapes):
+            if k:
+                tp = time.perf_counter()
+                nxt = lv[(k - 1) % 2]
+                cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=resampling)
+                cur = nxt
+                pyr_s += time.perf_counter() - tp
+            # level 0 of a large job: frames back into page-locked memory, as without overviews
+            encs.append(encode_band_tiles_device(ctx, cur.ptr, h, w, dtype, tile_size, arena,
+                                                 pinned=k == 0 and band.nbytes >= (64 << 20)))
+    finally:
+        for b in bufs:
+            b.close()
+    t1 = time.perf_counter()
+    tr6 = list(transform)[:6]
+    parts = []  # (headers, enc) per level, in file order
+    levels = []
+    fid, total = 0, 0
+    frames0: List[Dict] = []
+    for k, ((h, w), enc) in enumerate(zip(shapes, encs)):
+        lt = level_transform(tr6, k)
+        tk = geotiff.Affine(*lt) if k else transform
+        headers, frames, nbytes = streaming_headers(enc, tk, crs, w, h, tile_size, dtype, frame_id0=fid,
+                                                    byte_offset0=total)
+        parts.append((headers, enc, total))
+        fid += len(frames)
+        total += nbytes
+        if k == 0:
+            frames0 = frames
+        else:
+            levels.append({"level": k, "factor": 2 ** k, "width": w, "height": h, "transform": lt,
+                           "frames": frames})
+    index = {"crs": str(crs), "transform": list(transform), "width": W, "height": H, "tile_size": tile_size,
+             "frames": frames0, "overviews": {"resampling": resampling, "levels": levels}}
+    head = streaming_head(index)
+    t2 = time.perf_counter()
+    fd = os.open(output, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    try:
+        os.ftruncate(fd, len(head) + total)
+        t2b = time.perf_counter()
+        os.pwrite(fd, head, 0)
+        for headers, enc, start in parts:
+            write_tiles(fd, len(head) + start, headers, enc)
+    finally:
+        os.close(fd)
+    t3 = time.perf_counter()
+    tm.update(encode_s=t1 - t0, pyramid_s=pyr_s, index_s=t2 - t1, write_s=t3 - t2, open_truncate_s=t2b - t2,
+              total_s=t3 - t0)
+    return index
+
+
 def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Optional[str], output: Path,
                            tile_size: int = 1024, ctx: Optional[Context] = None,
-                           timings: Optional[Dict[str, float]] = None) -> Dict:
+                           timings: Optional[Dict[str, float]] = None, overviews: bool = False,
+                           resampling: str = "average", max_levels: Optional[int] = None) -> Dict:
     """cli.py:620-804 on an in-memory band-1 array: one GPU encode of every tile, headers and index on the host,
-    tiles written from the arena with parallel pwritev.  Returns the index; `timings` gets the stage seconds."""
+    tiles written from the arena with parallel pwritev.  Returns the index; `timings` gets the stage seconds.
+    overviews=True (extension) appends reduced-resolution levels (module docstring): `resampling` is "average" or
+    "nearest", `max_levels` caps their number; `timings` then also gets pyramid_s (inside encode_s)."""
     tm = timings if timings is not None else {}
+    if overviews:
+        return _create_streaming_overviews(band, transform, crs, output, tile_size, ctx, tm, resampling, max_levels)
     t0 = time.perf_counter()
     H, W = band.shape
     # large jobs: frames back into page-locked memory (DMA rate, no page faults) and written from there
@@ -257,12 +425,14 @@ def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Opt
 
 def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
                      ctx: Optional[Context] = None, timings: Optional[Dict[str, float]] = None,
-                     materialize: bool = False) -> Dict:
+                     materialize: bool = False, overviews: bool = False, resampling: str = "average",
+                     max_levels: Optional[int] = None) -> Dict:
     """cli.py:620-804 without the console output: writes the streaming file, returns the index.  Band 1 only
     (cli.py:698-699): an uncompressed band-sequential (or single-band) file is encoded straight from its memory map
     (no host copy of the band); otherwise its strips / tiles are decoded.  `timings` gets read_s + the stages of
     create_streaming_array.  materialize=True reads the band into host memory first (read_s is then the whole read;
-    otherwise the band's pages are read while the encode copies them, inside encode_s)."""
+    otherwise the band's pages are read while the encode copies them, inside encode_s).  overviews / resampling /
+    max_levels: as create_streaming_array."""
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
     with geotiff.TiffFile(input_file) as tf:
@@ -273,7 +443,8 @@ def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
             band = tf.read_rows(bands=[0])[0]
         tm["read_s"] = time.perf_counter() - t0
         transform = transform or geotiff.Affine(1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
-        index = create_streaming_array(band, transform, crs, output_file, tile_size, ctx, tm)
+        index = create_streaming_array(band, transform, crs, output_file, tile_size, ctx, tm, overviews=overviews,
+                                       resampling=resampling, max_levels=max_levels)
         del band
     tm["total_s"] = time.perf_counter() - t0
     return index
@@ -478,11 +649,13 @@ def fetch_tiles(src: Union[str, Path, Source], frames: Sequence[Dict], index_siz
 
 def extract_streaming(flac_url: Union[str, Path], output: Path, bbox: Optional[Sequence[float]] = None,
                       tile_id: Optional[int] = None, center: bool = False, last: bool = False,
-                      ctx: Optional[Context] = None) -> Dict:
-    """cli.py:875-1039: pick one tile, range-read it, decode it and write it as a GeoTIFF."""
+                      ctx: Optional[Context] = None, level: int = 0) -> Dict:
+    """cli.py:875-1039: pick one tile, range-read it, decode it and write it as a GeoTIFF.  `level` (extension):
+    pick among the tiles of that overview level (tile ids are the level's own frame ids); the GeoTIFF carries the
+    level tile's transform."""
     src = Source(flac_url)
     n, index = read_index(src)
-    f = select_frame(index, tile_id=tile_id, last=last, center=center, bbox=bbox)
+    f = select_frame(level_index(index, level), tile_id=tile_id, last=last, center=center, bbox=bbox)
     data = fetch_tiles(src, [f], n)[0]
     (arr, md), = TileDecoder(ctx).decode_streams([data])
     write_tiff_from_meta(Path(output), arr, md)
@@ -584,13 +757,15 @@ def _download_raster(dst, dtype, h: int, w: int) -> np.ndarray:
 
 
 def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: Optional[Context] = None,
-                        crop: bool = True):
+                        crop: bool = True, level: int = 0):
     """Extension: decode every tile intersecting bbox in one GPU batch straight into the raster window
     they cover, or (crop=True) into the whole-pixel window of the bbox itself (bbox_pixel_window): the tiles are
     placed and clipped on the device (decode_into_window), the host only receives the final window.  Returns
-    (array (1, h, w), window dict, transform list)."""
+    (array (1, h, w), window dict, transform list); with `level` > 0 the tiles, the window and the transform are that
+    overview level's."""
     src = Source(flac_url)
     n, index = read_index(src)
+    index = level_index(index, level)
     hits = intersecting(index, bbox)
     if not hits:
         raise LookupError(f"No tiles intersect with bbox {bbox}")
@@ -619,11 +794,12 @@ def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: 
     return out, win, list(wt)
 
 
-def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None):
-    """Every tile of a streaming file in one batched decode, placed into the full raster in device memory.
-    Returns (DeviceBuffer, dtype, index)."""
+def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0):
+    """Every tile of a streaming file (of overview level `level`) in one batched decode, placed into the level's full
+    raster in device memory.  Returns (DeviceBuffer, dtype, level_index(index, level))."""
     src = Source(flac_url)
     n, index = read_index(src)
+    index = level_index(index, level)
     frames = index["frames"]
     if not frames:
         raise ValueError("the streaming index lists no tiles")
@@ -632,16 +808,18 @@ def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None
     return dst, dtype, index
 
 
-def reconstruct(flac_url: Union[str, Path], ctx: Optional[Context] = None):
-    """The whole raster of a streaming file: (array (1, H, W), transform list)."""
-    dst, dtype, index = reconstruct_device(flac_url, ctx)
+def reconstruct(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0):
+    """The whole raster of a streaming file, or of one overview level: (array (1, H, W), transform list)."""
+    dst, dtype, index = reconstruct_device(flac_url, ctx, level)
     return _download_raster(dst, dtype, int(index["height"]), int(index["width"])), list(index["transform"])
 
 
-def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context] = None) -> Dict:
-    """extract-streaming --all: write the reconstruction as a GeoTIFF with the index's CRS and transform."""
-    arr, tr = reconstruct(flac_url, ctx)
+def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context] = None, level: int = 0) -> Dict:
+    """extract-streaming --all: write the reconstruction (of overview level `level`) as a GeoTIFF with the index's CRS
+    and the level's transform.  Returns level_index(index, level)."""
+    arr, tr = reconstruct(flac_url, ctx, level)
     _, index = read_index(flac_url)
+    index = level_index(index, level)
     crs = index.get("crs")
     epsg = int(crs.split(":")[1]) if crs and str(crs).upper().startswith("EPSG:") else None
     geotiff.write(Path(output), arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
@@ -652,22 +830,53 @@ def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optiona
     """create-streaming --verify: read the written file back (what is checked is what is on disk), decode it into a
     device raster through the window call, upload the source band and compare the two on the device
     (frs_compare_device).  Returns the un-wrapped differences as compare's ``exact`` key: n_different,
-    max_difference, mean_difference, first_difference."""
+    max_difference, mean_difference, first_difference.
+
+    A file with overviews has every level checked the same way: the pyramid is recomputed on the device from the
+    uploaded band with the index's ``resampling`` (frs_downsample2_device, level k from level k - 1) and each decoded
+    level is compared with it.  The result then also holds ``levels_checked`` (level 0 included) and ``levels``, one
+    dict per level (``level`` + the four keys above); the four top-level keys describe the first level that differs,
+    or level 0 when none does."""
     from .compare import _exact
     ctx = ctx or default_context()
     band = np.asarray(band)
     dst, dtype, index = reconstruct_device(flac_path, ctx)
+    bufs = [dst]
     try:
         H, W = int(index["height"]), int(index["width"])
         if band.shape != (H, W) or band.dtype != dtype:
             raise ValueError(f"source band {band.shape} {band.dtype} does not match the file's {(H, W)} {dtype}")
         srcbuf = ctx.alloc(band.nbytes)
-        try:
-            srcbuf.upload(band)
-            d = ctx.make_compare_desc(H, W, dtype)
-            bands = ctx.compare_device(srcbuf.ptr, dst.ptr, d)
-        finally:
-            srcbuf.close()
+        bufs.append(srcbuf)
+        srcbuf.upload(band)
+        d = ctx.make_compare_desc(H, W, dtype)
+        res = _exact(ctx.compare_device(srcbuf.ptr, dst.ptr, d), W)
+        ov = index.get("overviews")
+        if not ov:
+            return res
+        per_level = [dict(level=0, **res)]
+        cur, cur_desc = srcbuf, ctx.make_raster_desc(H, W, dtype)
+        for lv in sorted(ov.get("levels", []), key=lambda x: int(x["level"])):
+            k, h, w = int(lv["level"]), (cur_desc.height + 1) // 2, (cur_desc.width + 1) // 2
+            if k != len(per_level) or (int(lv["height"]), int(lv["width"])) != (h, w):
+                raise ValueError(f"overview level {k} is not the 2x reduction of the level before it")
+            nxt = ctx.alloc(h * w * dtype.itemsize)
+            bufs.append(nxt)
+            cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=ov["resampling"])
+            if cur is not srcbuf:
+                cur.close()
+            cur = nxt
+            got, gdt, _ = reconstruct_device(flac_path, ctx, k)
+            bufs.append(got)
+            if gdt != dtype:
+                raise ValueError(f"overview level {k} is {gdt}, the file's level 0 is {dtype}")
+            ex = _exact(ctx.compare_device(cur.ptr, got.ptr, ctx.make_compare_desc(h, w, dtype)), w)
+            got.close()
+            per_level.append(dict(level=k, **ex))
+        bad = [x for x in per_level if x["n_different"] != 0]
+        res = {key: (bad[0] if bad else per_level[0])[key] for key in res}
+        res.update(levels_checked=len(per_level), levels=per_level)
+        return res
     finally:
-        dst.close()
-    return _exact(bands, W)
+        for b in bufs:
+            b.close()

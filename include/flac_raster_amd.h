@@ -248,6 +248,32 @@ int frs_decode_tiles_window(frs_ctx *ctx, const uint8_t *blob_host, const int64_
                             int32_t bps, int32_t blocksize, const frs_tile_window *win, const double *data_min,
                             const double *data_max, const frs_raster_desc *dst, void *dst_host);
 
+/* One 2x reduction step of an overview pyramid: an H x W raster to ceil(H/2) x ceil(W/2).  The reference's streaming
+ * files hold one resolution; create-streaming --overviews (streaming.py) builds level k from level k-1 with this call
+ * and encodes every level with frs_encode_tiles_device.  Both rasters are band-planar [nbands][height][width] elements
+ * of the same dtype, each with its own row / band stride (frs_raster_desc, nbands 1..8).  Output pixel (r, x) covers
+ * source rows 2r .. min(2r+1, H-1) and columns 2x .. min(2x+1, W-1): n = 4, 2 or 1 source pixels; the edge blocks of odd
+ * sizes are partial, never padded.
+ *   FRS_RESAMPLE_NEAREST   the source pixel (2r, 2x), every dtype
+ *   FRS_RESAMPLE_AVERAGE   integers: floor((2s + n) / (2n)) of the exact 64-bit block sum s, the mean rounded half
+ *                          towards +infinity ((s + 2) >> 2 for n = 4: -1,-1,-1,-2 -> -1; -1,-2 -> -1; -3,-2 -> -2).
+ *                          Floats: ((a + b) + (c + d)) * 0.25 with a = (2r, 2x), b = (2r, 2x+1), c = (2r+1, 2x),
+ *                          d = (2r+1, 2x+1); (a + b) * 0.5 for n = 2; a for n = 1; every operation rounded in the dtype,
+ *                          NaN and +-inf as the expression gives them.  The definition is this library's own.
+ * Destination elements outside [height][width] are never written, the row padding of row_stride > width included (whole
+ * 16-byte chunks of a destination row by aligned 16-byte stores, the rest element by element; nothing is read past a
+ * source row's width or the last source row).  FRS_E_ARG: dst height or width not ceil(src / 2), a size < 1,
+ * row_stride < width, nbands outside 1..8 or unequal, dtypes unequal or unknown, a band_stride (nbands > 1) smaller than
+ * (height-1)*row_stride + width, an extent that overflows 63 bits, an unknown mode, a null pointer or one not aligned
+ * to the element size, and source and destination byte ranges (origin to the end of the last row) that overlap.
+ * Synchronous on the context stream; profile entry "pyramid".  frs_downsample2 takes host rasters: both are copied
+ * through the context's staging buffers (the destination goes up first and comes back whole, so its padding survives). */
+enum frs_resample { FRS_RESAMPLE_NEAREST = 0, FRS_RESAMPLE_AVERAGE = 1 };
+int frs_downsample2_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev, const frs_raster_desc *dst,
+                           void *dst_dev, int32_t mode);
+int frs_downsample2(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
+                    void *dst_host, int32_t mode);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
