@@ -33,6 +33,7 @@
 //                k_decode_frames_wave          the rest (32-bit, > 8 channels, long blocks): a wave per frame
 //   fallback list   frames the lane decoders decline go through k_decode_frames_wave_list
 //   k_denormalize   the unfused de-normalisation (denormalize_job)
+// The de-normalisation's arithmetic, fused into the decoders' stores or not, is frs_denormalize.h's.
 #include <stdlib.h>
 #include <string.h>
 
@@ -46,6 +47,7 @@
 #include "frs_frame_header.h"
 #include "frs_crc16_fold.h"
 #include "frs_decode_plan.h"
+#include "frs_denormalize.h"
 
 namespace frs {
 
@@ -876,14 +878,10 @@ struct DecOut {
 };
 
 __device__ inline void dn_store(const DecOut &o, int64_t i, int32_t pcm, float2 p) {
-    const float v = (float)(pcm >> o.shift) * (1.0f / 32768.0f);
+    const float v = dn_unit(dn_pcm16(pcm, o.shift));
     if (o.dtype == FRS_DT_F32) { static_cast<float *>(o.out)[i] = v; return; }
     if (o.dtype == FRS_DT_F64) { static_cast<double *>(o.out)[i] = (double)v; return; }
-    float a = __fadd_rn(v, 1.0f);
-    a = __fdiv_rn(a, 2.0f);
-    a = __fmul_rn(a, p.x);
-    a = __fadd_rn(a, p.y);
-    const int64_t r = (int64_t)rintf(a);
+    const int64_t r = dn_round64(dn_value4(v, p.x, p.y));
     switch (o.dtype) {
     case FRS_DT_U8: static_cast<uint8_t *>(o.out)[i] = (uint8_t)r; break;
     case FRS_DT_U16: static_cast<uint16_t *>(o.out)[i] = (uint16_t)r; break;
@@ -2578,11 +2576,9 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
     const bool dfast = (dt == FRS_DT_I16 || dt == FRS_DT_U16 || dt == FRS_DT_U8) && dout.shift == 0 &&
                        (obase & 7) == 0 && (bs & 7) == 0;
     const bool early = OPT && dfast;
-    const float dnx = dnp.x * (1.0f / 65536.0f);
-    auto dn1 = [&](int32_t x) -> uint32_t {  // (dn_bits_t's exact rewrite of ((x / 32768 + 1) / 2) * rng + mn)
-        const float a = __fadd_rn(__fmul_rn((float)((int32_t)((uint32_t)x << w) + 32768), dnx), dnp.y);
-        return (uint32_t)(int32_t)rintf(a);
-    };
+    const float dnx = dn_rng16(dnp.x);
+    // (frs_denormalize.h's two-operation form, the wasted-bit shift folded in)
+    auto dn1 = [&](int32_t x) -> uint32_t { return (uint32_t)dn_round32(dn_value2(x, w, dnx, dnp.y)); };
     int stored = 0;  // samples [0, stored) already stored (wave-uniform)
     if (!failed && i + 64 <= bs) {
         auto pk = [](int32_t hi, int32_t lo) { return ((uint32_t)hi << 16) | ((uint32_t)lo & 0xFFFFu); };
@@ -2668,9 +2664,7 @@ __global__ void __launch_bounds__(192) k_decode_frames_pipe(const uint8_t *blob,
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int32_t x = (int32_t)(int16_t)(wv[j >> 1] >> (16 * (j & 1)));
-                // (dn_bits_t's exact rewrite of ((x / 32768 + 1) / 2) * rng + mn)
-                const float a = __fadd_rn(__fmul_rn((float)((int32_t)((uint32_t)x << w) + 32768), dnx), dnp.y);
-                ob[j] = (uint32_t)(int32_t)rintf(a);
+                ob[j] = (uint32_t)dn_round32(dn_value2(x, w, dnx, dnp.y));
             }
             if (dt == FRS_DT_U8) {
                 reinterpret_cast<uint2 *>(static_cast<uint8_t *>(dout.out) + obase)[g] =
@@ -2888,11 +2882,9 @@ __device__ inline uint32_t dn_bits_t(const DecOut &o, int32_t pcm, float2 p) {
     } else if constexpr (OUT == kOutPlanar16) {
         return (uint32_t)pcm & 0xFFFFu;
     } else {
-        // ((v + 1) / 2) * rng + mn with v = h / 32768 (h = pcm >> shift, |h| < 2^24): (v + 1) / 2 = (h + 32768) 2^-16
-        // exactly, and scaling rng by 2^-16 instead is exact too, so one product and one sum round as in the
-        // reference's sequence; the rounded value is within the <= 16-bit output range, so an int32 conversion
-        const float a = __fadd_rn(__fmul_rn((float)((pcm >> o.shift) + 32768), p.x * (1.0f / 65536.0f)), p.y);
-        const int32_t r = (int32_t)rintf(a);
+        // frs_denormalize.h's two-operation form of ((v + 1) / 2) * rng + mn (h = pcm >> shift, no wasted-bit shift
+        // left to apply); the rounded value is within the <= 16-bit output range, so an int32 conversion
+        const int32_t r = dn_round32(dn_value2(dn_pcm16(pcm, o.shift), 0, dn_rng16(p.x), p.y));
         if constexpr (OUT == kOutU8) return (uint32_t)(uint8_t)r;
         else return (uint32_t)(uint16_t)r;
     }
@@ -3221,18 +3213,12 @@ template <typename O>
 __global__ void k_denormalize(const int32_t *pcm, int64_t n, int shift, float rng, float fmn, int is_float, O *out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int32_t p16 = pcm[i] >> shift;  // 32-bit streams: libsndfile int -> short keeps the high half
-    const float v = (float)((double)p16 / 32768.0);
+    const float v = dn_unit(dn_pcm16(pcm[i], shift));  // 32-bit streams: libsndfile int -> short keeps the high half
     if (is_float) {
         out[i] = (O)v;
         return;
     }
-    float a = __fadd_rn(v, 1.0f);
-    a = __fdiv_rn(a, 2.0f);
-    a = __fmul_rn(a, rng);
-    a = __fadd_rn(a, fmn);
-    const float r = rintf(a);
-    out[i] = (O)(int64_t)r;
+    out[i] = (O)dn_round64(dn_value4(v, rng, fmn));
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -3339,8 +3325,11 @@ static int stage_decode_tables(frs_ctx *ctx, DecodeCall &c, const int64_t *strea
     memcpy(htab + (ns + 1), fbase, tab);
     memcpy(htab + 2 * (ns + 1), pcm_off, tab);
     float2 *hdn = reinterpret_cast<float2 *>(htab + 3 * (ns + 1));
-    if (r.fused)  // python-float arithmetic first (data_max - data_min in double), then NEP 50 casts to float32
-        for (int s = 0; s < ns; s++) hdn[s] = make_float2((float)(dmax[s] - dmin[s]), (float)dmin[s]);
+    if (r.fused)
+        for (int s = 0; s < ns; s++) {
+            const DnPair p = dn_pair(dmin[s], dmax[s]);
+            hdn[s] = make_float2(p.rng, p.mn);
+        }
     if (r.tabs_by_arg) memcpy(c.stabs.v, htab, 3 * tab + dn_bytes);  // 6 int64 + one float2
     else FRS_HIP(hipMemcpyAsync(ctx->dec_soff.ptr, htab, 3 * tab + dn_bytes, hipMemcpyHostToDevice, st));
     c.hv = reinterpret_cast<int *>(reinterpret_cast<char *>(htab) + ((3 * tab + dn_bytes + 15) & ~(size_t)15));
@@ -3613,8 +3602,8 @@ int denormalize_job(frs_ctx *ctx, const int32_t *pcm_dev, int64_t n, int pcm_bps
                     int32_t out_dtype, void *out_dev) {
     hipStream_t st = ctx->stream;
     if (const int rc = check_unsynced(ctx)) return rc;
-    // python-float arithmetic first (data_max - data_min in double), then NEP 50 casts to float32
-    const float rng = (float)(dmax - dmin), fmn = (float)dmin;
+    const DnPair dp = dn_pair(dmin, dmax);
+    const float rng = dp.rng, fmn = dp.mn;
     const int sh = pcm_bps > 16 ? 16 : 0;
     const unsigned grid = (unsigned)((n + 255) / 256);
     if (n == 0) return FRS_OK;
