@@ -2572,7 +2572,7 @@ __device__ inline void residual_pair(const uint32_t *E, const uint32_t *C, int s
 constexpr uint64_t kFlagAgg = 1ull << 62, kFlagIncl = 2ull << 62, kValMask = (1ull << 62) - 1;
 
 // ------------------------------------------------------------------------------ k_encode_v3
-// Persistent work-groups of 4 waves; a WG takes a ticket of 4 consecutive frames (wave = frame), so
+// Persistent work-groups of NW waves (4 or 8); a WG takes a ticket of NW consecutive frames (wave = frame), so
 // tickets are handed out in frame order and every look-back waits only on frames already owned by
 // resident waves.  Frames on this path are always full 4096-sample blocks (host guarantees), so no
 // per-sample validity predicates exist: only lane 0's first `order` (<= 8) samples are masked, by
@@ -2583,8 +2583,10 @@ constexpr int kXpowHi = (kXpowBytes + 63) / 64;
 constexpr int kBufWordsV3 = kFrameWordsV3 + 64;  // + the overflow row of the code writer (lds_put_left)
 // a subframe slot (multi-channel streams): a frame's words, or the 17-bit VERBATIM side subframe (2177 words)
 constexpr int kSubWords = kFrameWordsV3 + 4;
+// NW: waves per work-group, one bit buffer each.  The LUT and the small tables come first, so that their LDS
+// addresses do not depend on NW.
+template <int NW = 4>
 struct EncV3Shared {
-    uint32_t bits[4][kBufWordsV3];
     int16_t lut[kLutCap];
     uint16_t xlo[64];           // x^(8m) mod P, m = 0..63
     uint16_t xhi[kXpowHi + 3];  // x^(8*64*(m - 3)) mod P (crc16_cols)
@@ -2592,10 +2594,13 @@ struct EncV3Shared {
     int ticket[2];
     int want[2];
     int lut_tile;
+    alignas(16) uint32_t bits[NW][kBufWordsV3];
 };
 // lut_gather_pairs forms LUT byte addresses mod 2^16: the LUT (the only LDS object of k_encode_v3 is this struct)
 // must end below 64 KiB
-static_assert(offsetof(EncV3Shared, lut) + sizeof(int16_t) * kLutCap <= 65536, "LUT beyond 64 KiB of LDS");
+static_assert(offsetof(EncV3Shared<8>, lut) + sizeof(int16_t) * kLutCap <= 65536, "LUT beyond 64 KiB of LDS");
+// two work-groups of 8 waves per CU (4 waves per SIMD) share its 160 KiB
+static_assert(sizeof(EncV3Shared<8>) <= 81920, "two 8-wave work-groups per CU");
 
 // Bank-aware layout of a wave's frame buffer.  Word w of the frame lives at row (w mod C), column (w / C) of a
 // 64-column matrix, C = ceil(words / 64) <= 34 chosen per frame: phys(w) = (w mod C) * 64 + w / C, so the LDS
@@ -2638,6 +2643,14 @@ __device__ inline void lds_put_bits2(uint32_t *buf, const FbMap &M, uint32_t pos
 __device__ inline void reg_fence(uint32_t *E) {
 #pragma unroll
     for (int m = 0; m < 36; m++) asm volatile("" : "+v"(E[m]));
+}
+
+// v, opaque to the optimiser at this point: what is computed from the result stays where it is written, so a
+// loop-invariant expression of the thread index is recomputed where it is used (a few VALU) and holds no register
+// across the rest of the loop
+__device__ inline uint32_t local_u32(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
 }
 
 // |a - b| + c on unsigned operands (v_sad_u32; the compiler does not form it from the pattern)
@@ -2761,7 +2774,9 @@ __device__ __forceinline__ void resolve_and_store(const EncodeParams &P, Pending
         uint8_t *dst = arena + prefix;
         const uint32_t a0 = min((uint32_t)fbytes, (uint32_t)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15));
         auto byte_at = [&](uint32_t b) -> uint8_t { return (uint8_t)(fbuf[M(b >> 2)] >> (24 - 8 * (b & 3))); };
-        if ((uint32_t)lane < a0) dst[lane] = byte_at((uint32_t)lane);
+        // (local: the lane's word address and byte shift are otherwise hoisted out of the ticket loop and held in
+        // VGPRs through the whole kernel)
+        if ((uint32_t)lane < a0) dst[lane] = byte_at(local_u32((uint32_t)lane));
         const uint32_t n16 = ((uint32_t)fbytes - a0) >> 4;
         const uint32_t r = a0 & 3, sb = a0 >> 2;
         uint4 *d16 = reinterpret_cast<uint4 *>(dst + a0);
@@ -3169,7 +3184,8 @@ static_assert(kFrameWordsV3 % 64 == 0 && kCrcRows <= frs::kCrcFoldSpan && kCrcBi
               "column CRC");
 static_assert(kCrcRows * 64 <= kBufWordsV3 && sizeof(g_xpow_hi) == sizeof(uint16_t) * (kXpowHi + 3),
               "the rows read (in groups of 8, below kCrcRows) are the buffer's; the factor table");
-__device__ __forceinline__ uint32_t crc16_cols(const uint32_t *fbuf, const FbMap &M, uint32_t body, const EncV3Shared &S,
+template <class Shared>
+__device__ __forceinline__ uint32_t crc16_cols(const uint32_t *fbuf, const FbMap &M, uint32_t body, const Shared &S,
                                                int lane) {
     const uint32_t c = frs::crc16_column<kCrcRows, 8>(fbuf + lane, 64, (int)M.c);
     const int m = max(0, (int)body + (kCrcBias - 4 * kCrcRows) - 4 * (int)M.c * lane);
@@ -3177,12 +3193,12 @@ __device__ __forceinline__ uint32_t crc16_cols(const uint32_t *fbuf, const FbMap
 }
 
 // ST: units of a two-channel stream's mid/side pass (chn 0..3 = left, right, mid, side; WIDE for the side signal).
-template <int DT, bool SUB = false, bool ST = false, bool WIDE = false>
+template <int DT, bool SUB = false, bool ST = false, bool WIDE = false, int NW = 4>
 __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *raster, const EncodeParams &P,
                                                 const TileGeom *__restrict__ tiles,
                                                 const TileNorm *__restrict__ norms,
                                                 const SubAnalysis *__restrict__ ana, uint8_t *arena, int64_t arena_cap,
-                                                int64_t *frame_off, uint64_t *status, int *err, EncV3Shared &S,
+                                                int64_t *frame_off, uint64_t *status, int *err, EncV3Shared<NW> &S,
                                                 int want, int64_t f, int lane, const int32_t *ftile,
                                                 PendingFrame &prev, const uint4 *hdr_tab, int hdr_n,
                                                 const uint32_t *pslots, const int64_t *pbytes, int chn = 0,
@@ -3190,7 +3206,7 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
                                                 int32_t *sub_est = nullptr) {
     using T = typename Elem<DT>::T;
     using Lane = std::conditional_t<WIDE, LaneWide, LanePairs>;
-    // (uni: a 1-D launch of 256 threads, so a wave's 64 threads share threadIdx.x >> 6)
+    // (uni: a 1-D launch of 64 NW threads, so a wave's 64 threads share threadIdx.x >> 6)
     uint32_t *fbuf = S.bits[uni_if<!WIDE>(threadIdx.x >> 6)];  // holds the pending frame `prev` (or zero) on entry
     const int t = ftile[f];  // (f is wave-uniform, see k_encode_v4: the frame's tables are scalar loads)
     const TileGeom g = tiles[t];
@@ -3673,11 +3689,15 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
 
 // SUB: the units are subframes -- (frame, channel) of a >= 3-channel stream, or of a two-channel stream's mid/side
 // pass (ST): left, right, mid in one launch, the 17-bit side signals (WIDE) in another.
-template <int DT, bool SUB = false, bool ST = false, bool WIDE = false>
-// (3 waves per SIMD for mono / >= 3-channel 16-bit units; 2 for the two-channel launches: convert_2band encode
-// 3.17 -> 2.78 ms against 1 wave per SIMD.  With the frame state scalar the mono instance takes 144 VGPRs of its 168
-// and L/R/M 159; the int32 side, in its vector form, 256 without a spill)
-__global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ? 2 : 3) : 1) k_encode_v4(const typename Elem<DT>::T *raster, EncodeParams P,
+// NW: waves per work-group (a ticket is NW consecutive units, one per wave); enc_nw() is each instance's: 8 for the
+// 16-bit (or narrower) mono instance, 4 for the subframe instances and the 32-bit types (250 VGPRs).
+template <int DT, bool SUB> constexpr int enc_nw() { return !SUB && sizeof(typename Elem<DT>::T) <= 2 ? 8 : 4; }
+template <int DT, bool SUB = false, bool ST = false, bool WIDE = false, int NW = 4>
+// (NW = 4: 3 waves per SIMD for >= 3-channel 16-bit units; 2 for the two-channel launches: convert_2band encode
+// 3.17 -> 2.78 ms against 1 wave per SIMD; L/R/M take 159 VGPRs; the int32 side, in its vector form, 256 without a
+// spill.  NW = 8, the 16-bit mono instance: two work-groups of 8 waves per CU are 4 waves per SIMD, which takes
+// <= 128 VGPRs and sizeof(EncV3Shared<8>) <= 80 KiB.  The second bound is waves per SIMD)
+__global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : sizeof(typename Elem<DT>::T) <= 2 ? (ST ? 2 : 3) : 1) k_encode_v4(const typename Elem<DT>::T *raster, EncodeParams P,
                                                   const TileGeom *__restrict__ tiles,
                                                   const TileNorm *__restrict__ norms, const int16_t *__restrict__ luts,
                                                   const SubAnalysis *__restrict__ ana, uint8_t *arena, int64_t arena_cap,
@@ -3686,7 +3706,7 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
                                                   int hdr_n, const uint32_t *__restrict__ pslots,
                                                   const int64_t *__restrict__ pbytes, uint32_t *sub_slots = nullptr,
                                                   int32_t *sub_bits = nullptr, int32_t *sub_est = nullptr) {
-    __shared__ __attribute__((aligned(16))) EncV3Shared S;
+    __shared__ __attribute__((aligned(16))) EncV3Shared<NW> S;
     // The tables this kernel only reads (tiles, norms, luts, ana, ftile, hdr_tab, pslots, pbytes) are written by
     // earlier kernels of the stream, never by this one: const __restrict__, so loads at wave-uniform addresses are
     // scalar loads.  The frame index is made provably wave-uniform below, which keeps everything decoded from it --
@@ -3696,12 +3716,12 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
     // register allocator spill 43 of a lane's samples across load_lane's normalisation switch (244 bytes of scratch
     // against 32).
     constexpr bool kUni = !WIDE;
-    // (uni: the launch is 1-D with 256 threads, so the 64 threads of a wave share threadIdx.x >> 6)
+    // (uni: the launch is 1-D with 64 NW threads, so the 64 threads of a wave share threadIdx.x >> 6)
     const int wave = (int)uni_if<kUni>(threadIdx.x >> 6), lane = threadIdx.x & 63;
     for (int i = threadIdx.x; i < 256; i += blockDim.x) S.crc8[i] = c_crc8[i];
     for (int i = threadIdx.x; i < 64; i += blockDim.x) S.xlo[i] = g_xpow_bytes[i];
     for (int i = threadIdx.x; i < kXpowHi + 3; i += blockDim.x) S.xhi[i] = g_xpow_hi[i];
-    for (int i = threadIdx.x; i < 4 * kBufWordsV3; i += blockDim.x) (&S.bits[0][0])[i] = 0;
+    for (int i = threadIdx.x; i < NW * kBufWordsV3; i += blockDim.x) (&S.bits[0][0])[i] = 0;
     if (threadIdx.x == 0) S.lut_tile = -1;
     PendingFrame prev;
     uint32_t *fbuf = S.bits[wave];
@@ -3719,13 +3739,13 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
         if (threadIdx.x == 0) {
             const int tk = atomicAdd(ticket_ctr, 1);
             S.ticket[sl] = tk;
-            const int64_t u0 = (int64_t)tk * 4;
+            const int64_t u0 = (int64_t)tk * NW;
             S.want[sl] = (u0 < nunits) ? ftile[SUB ? u0 / upf : u0] : -1;
         }
         __syncthreads();
         // (uni: sl is the same in every thread, and thread 0 wrote both slots before the barrier: every lane reads
         // the same LDS words)
-        const int64_t fbase = (int64_t)(int)uni_if<kUni>((uint32_t)S.ticket[sl]) * 4;
+        const int64_t fbase = (int64_t)(int)uni_if<kUni>((uint32_t)S.ticket[sl]) * NW;
         if (fbase >= nunits) break;
         const int want = (int)uni_if<kUni>((uint32_t)S.want[sl]);
         // (uni: S.lut_tile is written by thread 0 only, with a barrier between that write and this read)
@@ -3734,7 +3754,9 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
             if (tw.mode == kNormLut) {
                 const int64_t R = min(tw.imax - tw.imin, (int64_t)kLutCap - 1);
                 const int16_t *src = luts + (int64_t)want * kLutCap;
-                for (int64_t d = threadIdx.x; d <= R; d += blockDim.x) S.lut[d] = src[d];
+                // (local: keeps the thread's 64-bit source address out of the registers held across tickets)
+                for (int64_t d = NW == 8 ? local_u32(threadIdx.x) : threadIdx.x; d <= R; d += blockDim.x)
+                    S.lut[d] = src[d];
             }
             __syncthreads();
             if (threadIdx.x == 0) S.lut_tile = want;
@@ -3746,15 +3768,16 @@ __global__ void __launch_bounds__(256, sizeof(typename Elem<DT>::T) <= 2 ? (ST ?
                 const int chn = WIDE ? 3 : (int)(v - f * upf);
                 const TileGeom g = tiles[ftile[f]];
                 if (!(g.partial && f - g.frame_base == g.nframes - 1))
-                    encode_frame_v4<DT, true, ST, WIDE>(raster, P, tiles, norms, ana, arena, arena_cap, frame_off,
+                    encode_frame_v4<DT, true, ST, WIDE, NW>(raster, P, tiles, norms, ana, arena, arena_cap, frame_off,
                                                         status, err, S, want, f, lane, ftile, prev, hdr_tab, hdr_n,
                                                         pslots, pbytes, chn, sub_slots, sub_bits, sub_est);
             }
         } else {
             const int64_t f = fbase + wave;
             if (f < nunits)
-                encode_frame_v4<DT>(raster, P, tiles, norms, ana, arena, arena_cap, frame_off, status, err, S, want, f,
-                                    lane, ftile, prev, hdr_tab, hdr_n, pslots, pbytes);
+                encode_frame_v4<DT, false, false, false, NW>(raster, P, tiles, norms, ana, arena, arena_cap, frame_off,
+                                                             status, err, S, want, f, lane, ftile, prev, hdr_tab, hdr_n,
+                                                             pslots, pbytes);
         }
     }
     if constexpr (!SUB)
@@ -4132,14 +4155,22 @@ static int align_class(uintptr_t base, std::initializer_list<int> classes, std::
     return 0;
 }
 
-// A persistent kernel of 256-thread work-groups taking 4 units each: as many work-groups as fit the device (one
-// occupancy query per instantiation, kept in nwg_max; the same gfx950 target for every device), at most units / 4.
+// A persistent kernel of `threads`-thread work-groups taking `per_wg` units each: as many work-groups as fit the
+// device (one occupancy query per instantiation, kept in nwg_max; the same gfx950 target for every device), at most
+// units / per_wg.  need_wg: the work-groups per CU the kernel's shape was built for (0: whatever fits); fewer is an
+// error, not a slower launch.
 template <typename K, typename... Args>
-static int launch_resident(frs_ctx *ctx, K kern, int &nwg_max, int64_t units, Args... args) {
-    if (nwg_max == 0) FRS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nwg_max, kern, 256, 0));
+static int launch_resident(frs_ctx *ctx, K kern, int &nwg_max, int threads, int per_wg, int need_wg, int64_t units,
+                           Args... args) {
+    if (nwg_max == 0) FRS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nwg_max, kern, threads, 0));
+    if (nwg_max < need_wg) {
+        ctx->err = "encoder occupancy: " + std::to_string(nwg_max) + " work-groups of " + std::to_string(threads) +
+                   " threads per CU, built for " + std::to_string(need_wg);
+        return FRS_E_HIP;
+    }
     int64_t grid = (int64_t)std::max(1, nwg_max) * ctx->num_cus;
-    grid = std::min<int64_t>(grid, (units + 3) / 4);
-    kern<<<(unsigned)grid, 256, 0, ctx->stream>>>(args...);
+    grid = std::min<int64_t>(grid, (units + per_wg - 1) / per_wg);
+    kern<<<(unsigned)grid, threads, 0, ctx->stream>>>(args...);
     return FRS_OK;
 }
 
@@ -4524,7 +4555,10 @@ static int encode_fast_mono(EncodeJob<DT> &J, int64_t *dpbytes) {
     hipEvent_t ev;
     static int nwg_max = 0;
     prof_begin(ctx, "encode", &ev);
-    if (const int rc = launch_resident(ctx, k_encode_v4<DT>, nwg_max, nframes, J.raster, J.P, J.dtiles, J.dnorms,
+    constexpr int NW = enc_nw<DT, false>();
+    // (8 waves: built for two work-groups per CU, 4 waves per SIMD)
+    if (const int rc = launch_resident(ctx, k_encode_v4<DT, false, false, false, NW>, nwg_max, 64 * NW, NW,
+                                       NW == 8 ? 2 : 0, nframes, J.raster, J.P, J.dtiles, J.dnorms,
                                        ctx->luts.as<int16_t>(), J.dana, J.arena, J.arena_cap,
                                        ctx->frame_off.as<int64_t>(), dstatus, ticket, J.err_flag,
                                        ctx->frame_tile.as<int32_t>(), ctx->hdr_tab.as<uint4>(), hdr_n,
@@ -4588,8 +4622,8 @@ static int encode_fast_multi(EncodeJob<DT> &J, int64_t *dpbytes) {
     hipEvent_t ev;
     prof_begin(ctx, "encode", &ev);
     auto launch = [&](auto kern, int &nwg_max, int64_t units, int *tk) {
-        return launch_resident(ctx, kern, nwg_max, units, J.raster, P, J.dtiles, J.dnorms, ctx->luts.as<int16_t>(),
-                               J.dana, J.arena, J.arena_cap, ctx->frame_off.as<int64_t>(), dstatus, tk, J.err_flag,
+        return launch_resident(ctx, kern, nwg_max, 256, 4, 0, units, J.raster, P, J.dtiles, J.dnorms,
+                               ctx->luts.as<int16_t>(), J.dana, J.arena, J.arena_cap, ctx->frame_off.as<int64_t>(), dstatus, tk, J.err_flag,
                                dftile, ctx->hdr_tab.as<uint4>(), 0, ctx->slots.as<uint32_t>(), dpbytes, dsub, dsbits,
                                dsest);
     };
