@@ -40,12 +40,15 @@ EXPORTS = (
     "frs_compare_device", "frs_compare",
     "frs_place_tiles_device", "frs_decode_tiles_window_device", "frs_decode_tiles_window",
     "frs_downsample2_device", "frs_downsample2",
+    "frs_resample_window_device", "frs_resample_window",
 )
 
 # enum frs_resample
 RESAMPLE_NEAREST = 0
 RESAMPLE_AVERAGE = 1
+RESAMPLE_BILINEAR = 2  # frs_resample_window* only
 RESAMPLE_CODES = {"nearest": RESAMPLE_NEAREST, "average": RESAMPLE_AVERAGE}
+WINDOW_RESAMPLE_CODES = {"nearest": RESAMPLE_NEAREST, "bilinear": RESAMPLE_BILINEAR, "average": RESAMPLE_AVERAGE}
 
 # launch constants of k_compare (csrc/frs_compare.hip: kCmpBlock, kCmpUnroll, kCmpMaxGroups): a work-group step covers
 # COMPARE_BLOCK * COMPARE_UNROLL 16-byte vectors of each raster, and a band gets one work-group per step up to
@@ -122,6 +125,14 @@ class RasterDesc(ctypes.Structure):
         ("height", ctypes.c_int64), ("width", ctypes.c_int64),
         ("row_stride", ctypes.c_int64), ("band_stride", ctypes.c_int64),
         ("dtype", ctypes.c_int32), ("nbands", ctypes.c_int32),
+    ]
+
+
+class WindowMap(ctypes.Structure):
+    """frs_window_map: the source rectangle in pixel-edge coordinates of the source buffer, and the fill value"""
+    _fields_ = [
+        ("x0", ctypes.c_double), ("y0", ctypes.c_double), ("width", ctypes.c_double), ("height", ctypes.c_double),
+        ("fill", ctypes.c_double),
     ]
 
 
@@ -242,6 +253,11 @@ def load_library(path: Optional[os.PathLike] = None):
         L.frs_downsample2_device.argtypes = ds_args
         L.frs_downsample2.restype = i32
         L.frs_downsample2.argtypes = ds_args
+        rw_args = [ctxp, rdp, vp, rdp, vp, ctypes.POINTER(WindowMap), i32]
+        L.frs_resample_window_device.restype = i32
+        L.frs_resample_window_device.argtypes = rw_args
+        L.frs_resample_window.restype = i32
+        L.frs_resample_window.argtypes = rw_args
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -725,6 +741,49 @@ class Context:
         out = np.zeros(((nb,) if a.ndim == 3 else ()) + (dd.height, dd.width), dtype=a.dtype)
         self._check(self.lib.frs_downsample2(self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out),
                                              self._resample_code(mode)))
+        return out
+
+    # ---- windowed resample
+    @staticmethod
+    def _window_resample_code(mode) -> int:
+        if isinstance(mode, str):
+            if mode not in WINDOW_RESAMPLE_CODES:
+                raise ValueError(f"resampling must be one of {list(WINDOW_RESAMPLE_CODES)}, got {mode!r}")
+            return WINDOW_RESAMPLE_CODES[mode]
+        return int(mode)
+
+    @staticmethod
+    def _window_map(rect, fill) -> WindowMap:
+        if isinstance(rect, WindowMap):
+            return rect
+        x0, y0, width, height = (float(v) for v in rect)
+        return WindowMap(x0, y0, width, height, float(fill))
+
+    def resample_window_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, dst_desc: RasterDesc, rect,
+                               mode, fill=0) -> None:
+        """frs_resample_window_device: the rectangle rect = (x0, y0, width, height), in pixel-edge coordinates of the
+        device raster at src_ptr (laid out as src_desc), resampled onto the whole of the device raster at dst_ptr
+        (dst_desc).  `mode` is "nearest", "bilinear", "average" or an enum frs_resample value; destination pixels the
+        source does not cover get `fill`.  `rect` may be a WindowMap, which then carries its own fill."""
+        m = self._window_map(rect, fill)
+        self._check(self.lib.frs_resample_window_device(self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr),
+                                                        ctypes.byref(dst_desc), ctypes.c_void_p(dst_ptr),
+                                                        ctypes.byref(m), self._window_resample_code(mode)))
+
+    def resample_window(self, a: np.ndarray, rect, out_shape, mode="average", fill=0) -> np.ndarray:
+        """frs_resample_window on a host raster ((bands, H, W) or (H, W)): rect = (x0, y0, width, height) of it as an
+        array of out_shape = (h, w) pixels per band, same rank and dtype."""
+        a = np.ascontiguousarray(a)
+        if a.ndim not in (2, 3) or a.dtype not in DTYPE_CODES or a.size == 0:
+            raise ValueError("resample_window needs a non-empty (bands, H, W) or (H, W) array of a raster dtype")
+        h, w = (int(v) for v in out_shape)
+        nb = a.shape[0] if a.ndim == 3 else 1
+        sd = self.make_raster_desc(a.shape[-2], a.shape[-1], a.dtype, nbands=nb)
+        dd = self.make_raster_desc(h, w, a.dtype, nbands=nb)
+        out = np.zeros(((nb,) if a.ndim == 3 else ()) + (max(h, 0), max(w, 0)), dtype=a.dtype)
+        m = self._window_map(rect, fill)
+        self._check(self.lib.frs_resample_window(self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out),
+                                                 ctypes.byref(m), self._window_resample_code(mode)))
         return out
 
     # ---- bench helpers

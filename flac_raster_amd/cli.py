@@ -186,9 +186,38 @@ def extract_streaming(
     max_size: Optional[int] = typer.Option(None, "--max-size", min=1,
                                            help="Extension: with --all or --bbox --mosaic, read the finest level at "
                                                 "which the result is at most N pixels on its longer side"),
+    out_size: Optional[str] = typer.Option(None, "--out-size",
+                                           help="Extension: with --bbox, return the box as exactly WxH pixels, "
+                                                "resampled on the GPU from the overview level that fits"),
+    resampling: Optional[str] = typer.Option(None, "--resampling",
+                                             help="With --out-size: nearest, bilinear or average (default)"),
+    fill: Optional[float] = typer.Option(None, "--fill", help="With --out-size: value of pixels outside the raster "
+                                                              "(default 0)"),
 ):
     """Extract tiles from Netflix-style streaming FLAC files"""
     from . import streaming
+    # --out-size: every rule is checked before anything is read
+    size = None
+    if out_size is None and (resampling is not None or fill is not None):
+        typer.echo("Error: --resampling and --fill work with --out-size only", err=True)
+        raise typer.Exit(1)
+    if out_size is not None:
+        if bbox is None:
+            typer.echo("Error: --out-size needs --bbox", err=True)
+            raise typer.Exit(1)
+        if mosaic or all_tiles or tile_id is not None or center or last or max_size is not None:
+            typer.echo("Error: --out-size cannot be combined with --mosaic, --all, --tile-id, --center, --last or "
+                       "--max-size", err=True)
+            raise typer.Exit(1)
+        parts = out_size.lower().split("x")
+        if len(parts) != 2 or not all(p.isascii() and p.isdigit() for p in parts) or min(int(p) for p in parts) < 1:
+            typer.echo(f"Error: --out-size must be WxH with W and H >= 1, got {out_size!r}", err=True)
+            raise typer.Exit(1)
+        size = (int(parts[0]), int(parts[1]))
+        resampling = "average" if resampling is None else resampling
+        if resampling not in streaming.RESAMPLING_READ:
+            typer.echo(f"Error: --resampling must be one of {', '.join(streaming.RESAMPLING_READ)}", err=True)
+            raise typer.Exit(1)
     # --all takes no tile selection: checked before anything is read
     if all_tiles and (bbox is not None or tile_id is not None or center or last):
         typer.echo("Error: --all cannot be combined with --bbox, --tile-id, --center or --last", err=True)
@@ -221,7 +250,17 @@ def extract_streaming(
                     wpx, hpx = max(win["width"], 1), max(win["height"], 1)
             lvl = streaming.pick_level(index, wpx, hpx, max_size)
         at = f" (level {lvl})" if level is not None or max_size is not None else ""
-        if all_tiles:
+        if size is not None:
+            from . import geotiff
+            _, index = streaming.read_index(flac_url)
+            req = streaming.window_request(index, coords, size[0], size[1], level)
+            arr, tr = streaming.read_window(flac_url, coords, size[0], size[1], resampling=resampling, level=level,
+                                            fill=0 if fill is None else fill)
+            crs = index.get("crs")
+            epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
+            geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
+            typer.echo(f"SUCCESS: window {size[0]}x{size[1]} (level {req['level']}, {resampling}) -> {output}")
+        elif all_tiles:
             index = streaming.extract_all(flac_url, output, level=lvl)
             typer.echo(f"SUCCESS: Extracted all {len(index['frames'])} tiles to {output}{at}")
         elif mosaic and coords is not None:

@@ -1,0 +1,292 @@
+// frs_window.hip -- resample a rectangle of a band-planar raster onto a destination grid of any size
+// (frs_resample_window*), by the arithmetic of frs_window_map.h (nearest, bilinear, or the area-weighted average).
+//
+// There is no reference path: the reference reads whole tiles at the one resolution a file holds.  It is the last
+// stage of streaming.read_window: the tiles a bounding box needs are decoded and placed into a device window
+// (frs_decode_tiles_window_device), this kernel maps the box onto the W x H pixels the caller asked for, and only those
+// cross to the host.
+//
+//   k_resample_window   grid (gx, gy, nbands), 256 threads.  Work-group (bx, by, band) owns destination rows by,
+//                       by + gy, ... of the band and, of each, the 16-byte chunks bx * 256 + lane, striding gx * 256.
+//                       Row and band come from the block index alone: the row's taps, weights and validity
+//                       (win_nearest / win_linear / win_area of the y axis), the source row pointers and the row's
+//                       alignment are uniform over the work-group.
+//
+// Store side, as in frs_place.hip and frs_pyramid.hip: a destination row is cut at the 16-byte boundaries of the
+// DESTINATION; a chunk that lies wholly inside the row leaves as one aligned 16-byte store per lane, the first and last
+// chunk of a row that starts or ends off a boundary go element by element.  Destination elements outside
+// [height][width] are never written.  Load side: the taps of neighbouring outputs lie `step` source pixels apart, a
+// number only known at run time, so each tap is one element-sized global load (a lane's 16 / ES outputs read
+// neighbouring addresses, the lines stay in the vector L1 between them).  Every tap index comes out of frs_window_map.h
+// inside [0, N): nothing is read outside the source's [H][W].  The average's tap loops are not capped (a 150x reduction
+// reads 150 x 150 taps per output).  No LDS, no atomics, no init pass.
+//
+// One instantiation per (dtype, mode): the conversion to double and the rounding differ per dtype, and there is no
+// per-element switch on either.
+#include <algorithm>
+
+#include "frs_internal.h"
+#include "frs_window_map.h"
+
+namespace frs {
+
+constexpr int kWinBlock = 256;        // threads per work-group
+constexpr int kWinMaxGridY = 32768;   // destination rows beyond this are strided over
+
+struct WinParams {
+    int64_t src_h, src_w, dst_h, dst_w;
+    int64_t src_row_stride, src_band_stride, dst_row_stride, dst_band_stride;
+    double x0, y0, width, height, fill;
+};
+
+// What a destination row needs of the y axis, and one output of that row.
+template <int MODE, typename T> struct WinRow;
+
+template <typename T> struct WinRow<kWindowNearest, T> {
+    const T *s0;
+    bool valid;
+    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r) {
+        const WinNearest n = win_nearest(ay, r);
+        valid = n.valid, s0 = src + n.i * P.src_row_stride;
+    }
+    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
+        const WinNearest n = win_nearest(ax, x);
+        return valid && n.valid ? s0[n.i] : fill;
+    }
+};
+
+template <typename T> struct WinRow<kWindowBilinear, T> {
+    const T *s0, *s1;
+    double t;
+    bool valid;
+    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r) {
+        const WinLinear l = win_linear(ay, r);
+        valid = l.valid, t = l.t;
+        s0 = src + l.i0 * P.src_row_stride, s1 = src + l.i1 * P.src_row_stride;
+    }
+    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
+        const WinLinear l = win_linear(ax, x);
+        if (!(valid && l.valid)) return fill;
+        const double a = (double)s0[l.i0], b = (double)s0[l.i1], c = (double)s1[l.i0], d = (double)s1[l.i1];
+        return win_result<T>(win_bilinear_value(a, b, c, d, l.t, t));
+    }
+};
+
+template <typename T> struct WinRow<kWindowAverage, T> {
+    const T *src;
+    int64_t row_stride;
+    WinArea ry;
+    __host__ __device__ WinRow(const T *src_, const WinParams &P, const WinAxis &ay, int64_t r)
+        : src(src_), row_stride(P.src_row_stride), ry(win_area(ay, r)) {}
+    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
+        const WinArea rx = win_area(ax, x);
+        if (!(ry.valid && rx.valid)) return fill;
+        double sum = 0.0;
+        for (int64_t j = ry.i0; j < ry.i1; j++) {
+            const T *s = src + j * row_stride;
+            double row = 0.0;
+            for (int64_t i = rx.i0; i < rx.i1; i++) row = row + win_area_weight(rx, i) * (double)s[i];
+            sum = sum + win_area_weight(ry, j) * row;
+        }
+        return win_result<T>(win_area_value(sum, rx, ry));
+    }
+};
+
+// One lane's share of a work-group: lane tid of work-group (bx of gx, by of gy) of one band (src / dst are the band's
+// origins).  (Plain C++, so that a host program can run it lane by lane against a direct evaluation.)
+template <int MODE, typename T>
+__host__ __device__ inline void window_group(const T *__restrict__ src, T *__restrict__ dst, const WinParams &P,
+                                             int64_t bx, int64_t gx, int64_t by, int64_t gy, uint32_t tid) {
+    constexpr int ES = (int)sizeof(T);
+    constexpr int VE = 16 / ES;  // outputs per 16-byte chunk
+    const int64_t w = P.dst_w;
+    const WinAxis ax = win_axis(P.x0, P.width, P.dst_w, P.src_w);
+    const WinAxis ay = win_axis(P.y0, P.height, P.dst_h, P.src_h);
+    const T fill = win_result<T>(P.fill);
+    for (int64_t r = by; r < P.dst_h; r += gy) {
+        const WinRow<MODE, T> row(src, P, ay, r);
+        T *d = dst + r * P.dst_row_stride;
+        const int64_t first = (int64_t)(reinterpret_cast<uintptr_t>(d) & 15) / ES;
+        const int64_t cpr = (first + w + VE - 1) / VE;  // chunks the row touches
+        for (int64_t k = bx * kWinBlock + tid; k < cpr; k += gx * kWinBlock) {
+            // chunk k holds the row's outputs [pa, pb)
+            const int64_t p0 = k * VE - first;
+            const int64_t pa = p0 < 0 ? 0 : p0, pb = std::min<int64_t>(p0 + VE, w);
+            T o[VE];
+#pragma unroll
+            for (int e = 0; e < VE; e++) {
+                const int64_t x = p0 + e;
+                o[e] = x >= pa && x < pb ? row.pixel(ax, x, fill) : fill;
+            }
+            if (pb - pa == VE) {  // a whole chunk: d + pa is 16-byte aligned
+                uint4 v;
+                __builtin_memcpy(&v, o, 16);
+                *reinterpret_cast<uint4 *>(d + pa) = v;
+            } else {  // head or tail of the row
+#pragma unroll
+                for (int e = 0; e < VE; e++) {
+                    const int64_t x = p0 + e;
+                    if (x >= pa && x < pb) d[x] = o[e];
+                }
+            }
+        }
+    }
+}
+
+template <int MODE, typename T>
+__global__ void __launch_bounds__(kWinBlock) k_resample_window(const T *__restrict__ src, T *__restrict__ dst,
+                                                               WinParams P) {
+    const int64_t band = blockIdx.z;
+    window_group<MODE, T>(src + band * P.src_band_stride, dst + band * P.dst_band_stride, P, blockIdx.x, gridDim.x,
+                          blockIdx.y, gridDim.y, threadIdx.x);
+}
+
+template <typename T>
+static void launch_window(hipStream_t st, dim3 grid, int32_t mode, const void *src, void *dst, const WinParams &P) {
+    const T *s = static_cast<const T *>(src);
+    T *d = static_cast<T *>(dst);
+    if (mode == FRS_RESAMPLE_NEAREST) k_resample_window<kWindowNearest, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
+    else if (mode == FRS_RESAMPLE_BILINEAR) k_resample_window<kWindowBilinear, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
+    else k_resample_window<kWindowAverage, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
+}
+
+// The arguments are already validated (check_window_args below).  Synchronous on the context stream.
+static int window_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d,
+                      void *dst_dev, const frs_window_map *map, int32_t mode) {
+    const int es = dtype_size(d->dtype);
+    WinParams P;
+    P.src_h = s->height, P.src_w = s->width, P.dst_h = d->height, P.dst_w = d->width;
+    P.src_row_stride = s->row_stride, P.src_band_stride = s->band_stride;
+    P.dst_row_stride = d->row_stride, P.dst_band_stride = d->band_stride;
+    P.x0 = map->x0, P.y0 = map->y0, P.width = map->width, P.height = map->height, P.fill = map->fill;
+    // chunks of the longest row (one more when it starts off a boundary); whole steps only, the rest is strided over
+    const int64_t cpr = (d->width + 16 / es - 1) / (16 / es) + 1;
+    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(cpr / kWinBlock, 65535));
+    const dim3 grid((unsigned)gx, (unsigned)std::min<int64_t>(d->height, kWinMaxGridY), (unsigned)d->nbands);
+    hipStream_t st = ctx->stream;
+    hipEvent_t ev;
+    prof_begin(ctx, "resample", &ev);
+    switch (d->dtype) {
+    case FRS_DT_U8: launch_window<uint8_t>(st, grid, mode, src_dev, dst_dev, P); break;
+    case FRS_DT_U16: launch_window<uint16_t>(st, grid, mode, src_dev, dst_dev, P); break;
+    case FRS_DT_I16: launch_window<int16_t>(st, grid, mode, src_dev, dst_dev, P); break;
+    case FRS_DT_I32: launch_window<int32_t>(st, grid, mode, src_dev, dst_dev, P); break;
+    case FRS_DT_U32: launch_window<uint32_t>(st, grid, mode, src_dev, dst_dev, P); break;
+    case FRS_DT_F32: launch_window<float>(st, grid, mode, src_dev, dst_dev, P); break;
+    default: launch_window<double>(st, grid, mode, src_dev, dst_dev, P); break;
+    }
+    prof_end(ctx, "resample", ev);
+    FRS_HIP(hipGetLastError());
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    return FRS_OK;
+}
+
+// elements from a raster's origin to the end of its last row, or -1 when that does not fit 63 bits (with room for the
+// element size)
+static int64_t window_extent(const frs_raster_desc *d) {
+    int64_t x, y;
+    if (__builtin_mul_overflow((int64_t)d->nbands - 1, d->nbands > 1 ? d->band_stride : 0, &x) ||
+        __builtin_mul_overflow(d->height - 1, d->row_stride, &y) || __builtin_add_overflow(x, y, &x) ||
+        __builtin_add_overflow(x, d->width, &x) || x > (INT64_MAX >> 4))
+        return -1;
+    return x;
+}
+
+// argument checks of frs_resample_window*, before anything is sized, copied or launched
+static int check_window_desc(frs_ctx *ctx, const frs_raster_desc *d) {
+    if (!d) { ctx->err = "null desc"; return FRS_E_ARG; }
+    if (d->height < 1 || d->width < 1) { ctx->err = "resample: height and width must be >= 1"; return FRS_E_ARG; }
+    if (d->row_stride < d->width) { ctx->err = "row_stride < width"; return FRS_E_ARG; }
+    if (d->nbands < 1 || d->nbands > kMaxChannels) { ctx->err = "nbands must be 1..8"; return FRS_E_ARG; }
+    if (dtype_size(d->dtype) == 0) { ctx->err = "bad dtype"; return FRS_E_ARG; }
+    if (window_extent(d) < 0) { ctx->err = "resample: raster extent overflows"; return FRS_E_ARG; }
+    if (d->nbands > 1 && d->band_stride < (d->height - 1) * d->row_stride + d->width) {
+        ctx->err = "band_stride too small";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
+static bool window_coord_ok(double v) { return v == v && v > -4503599627370496.0 && v < 4503599627370496.0; }  // 2^52
+
+static int check_window_args(frs_ctx *ctx, const frs_raster_desc *src, const frs_raster_desc *dst,
+                             const frs_window_map *map, int32_t mode) {
+    if (int rc = check_window_desc(ctx, src)) return rc;
+    if (int rc = check_window_desc(ctx, dst)) return rc;
+    if (src->dtype != dst->dtype || src->nbands != dst->nbands) {
+        ctx->err = "resample: source and destination differ in dtype or nbands";
+        return FRS_E_ARG;
+    }
+    if (mode != FRS_RESAMPLE_NEAREST && mode != FRS_RESAMPLE_AVERAGE && mode != FRS_RESAMPLE_BILINEAR) {
+        ctx->err = "resample: bad mode";
+        return FRS_E_ARG;
+    }
+    if (!map) { ctx->err = "null map"; return FRS_E_ARG; }
+    // (a non-finite value fails window_coord_ok: NaN compares false, +-inf is out of range)
+    if (!window_coord_ok(map->x0) || !window_coord_ok(map->y0) || !window_coord_ok(map->width) ||
+        !window_coord_ok(map->height) || !window_coord_ok(map->x0 + map->width) ||
+        !window_coord_ok(map->y0 + map->height)) {
+        ctx->err = "resample: the rectangle must be finite, with coordinates below 2^52 in magnitude";
+        return FRS_E_ARG;
+    }
+    if (!(map->fill - map->fill == 0.0)) { ctx->err = "resample: fill must be finite"; return FRS_E_ARG; }
+    if (!(map->width > 0.0) || !(map->height > 0.0)) {
+        ctx->err = "resample: the rectangle's width and height must be > 0";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
+static size_t window_bytes(const frs_raster_desc *d) { return (size_t)window_extent(d) * (size_t)dtype_size(d->dtype); }
+
+// null, misaligned or overlapping rasters
+static int check_window_pointers(frs_ctx *ctx, const frs_raster_desc *src, const void *sp, const frs_raster_desc *dst,
+                                 const void *dp) {
+    const uintptr_t es = (uintptr_t)dtype_size(dst->dtype);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(sp), b = reinterpret_cast<uintptr_t>(dp);
+    if (!sp || !dp || a % es || b % es) {
+        ctx->err = "resample: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    if (a < b + window_bytes(dst) && b < a + window_bytes(src)) {
+        ctx->err = "resample: source and destination overlap";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
+}  // namespace frs
+
+extern "C" {
+
+int frs_resample_window_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                               const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map, int32_t mode) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = frs::check_window_args(ctx, src, dst, map, mode)) return rc;
+    if (int rc = frs::check_window_pointers(ctx, src, src_dev, dst, dst_dev)) return rc;
+    FRS_HIP(hipSetDevice(ctx->device));
+    return frs::window_job(ctx, src, src_dev, dst, dst_dev, map, mode);
+}
+
+int frs_resample_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
+                        void *dst_host, const frs_window_map *map, int32_t mode) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = frs::check_window_args(ctx, src, dst, map, mode)) return rc;
+    if (int rc = frs::check_window_pointers(ctx, src, src_host, dst, dst_host)) return rc;
+    const size_t sbytes = frs::window_bytes(src), dbytes = frs::window_bytes(dst);
+    FRS_HIP(hipSetDevice(ctx->device));
+    FRS_HIP(ctx->raster_stage.ensure(sbytes));
+    FRS_HIP(ctx->arena_stage.ensure(dbytes));
+    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
+    // the destination goes up first: its row and band padding comes back as it was
+    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = frs::window_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, map, mode)) return rc;
+    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    return FRS_OK;
+}
+
+}  // extern "C"

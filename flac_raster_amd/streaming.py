@@ -794,6 +794,125 @@ def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: 
     return out, win, list(wt)
 
 
+RESAMPLING_READ = ("nearest", "bilinear", "average")
+
+
+def pick_level_for_scale(index: Dict, scale: float) -> int:
+    """The coarsest level k the file holds with 2**k <= scale (`scale`: level-0 pixels per output pixel), so that the
+    resample that follows still reduces, never enlarges, what it reads; 0 when scale < 1 or the file holds level 0
+    only.  Pure."""
+    best = 0
+    for k in overview_levels(index):
+        if k > best and float(2 ** k) <= scale:
+            best = k
+    return best
+
+
+def window_request(index: Dict, bbox: Sequence[float], out_w: int, out_h: int, level: Optional[int] = None) -> Dict:
+    """What read_window needs to return bbox = [xmin, ymin, xmax, ymax] as out_w x out_h pixels, from the index alone
+    (pure).  The transform must be north-up (b = d = 0, a > 0, e < 0), else ValueError.
+      scale       max(bbox width in level-0 pixels / out_w, bbox height in level-0 pixels / out_h)
+      level       pick_level_for_scale(index, scale), or `level` when given
+      window      the level's whole pixels to decode: columns floor(x) - 1 .. ceil(x + width) + 1 and rows floor(y) - 1
+                  .. ceil(y + height) + 1 of the bbox's fractional pixel rectangle (x, y, width, height) in that level,
+                  clipped to the level's raster.  The one-pixel margin serves bilinear's second tap and absorbs the last
+                  hi(j) landing an ulp past the rectangle.  Width and height are 0 when nothing is left.
+      rect        (x0, y0, width, height): the rectangle relative to the window's origin, as frs_window_map takes it
+      frames      the level's index entries whose `window` intersects the window, in index order
+      transform   of the result: [(xmax - xmin) / out_w, 0, xmin, 0, -(ymax - ymin) / out_h, ymax]"""
+    out_w, out_h = int(out_w), int(out_h)
+    if out_w < 1 or out_h < 1:
+        raise ValueError("the output size must be at least 1 x 1")
+    xmin, ymin, xmax, ymax = (float(v) for v in bbox)
+    if not (xmax > xmin and ymax > ymin):
+        raise ValueError("bbox must be xmin,ymin,xmax,ymax with xmax > xmin and ymax > ymin")
+    a0, b0, _, d0, e0, _ = (float(v) for v in list(index["transform"])[:6])
+    if b0 != 0 or d0 != 0:
+        raise ValueError("a windowed read needs a north-up transform (rotation terms b and d must be 0)")
+    if not (a0 > 0 and e0 < 0):
+        raise ValueError("a windowed read needs a north-up transform (a > 0, e < 0)")
+    scale = max(((xmax - xmin) / a0) / out_w, ((ymin - ymax) / e0) / out_h)
+    k = pick_level_for_scale(index, scale) if level is None else int(level)
+    li = level_index(index, k)
+    a, _, c, _, e, f = (float(v) for v in list(li["transform"])[:6])
+    W, H = int(li["width"]), int(li["height"])
+    x, y = (xmin - c) / a, (ymax - f) / e
+    width, height = (xmax - xmin) / a, (ymin - ymax) / e
+    c0, c1 = max(math.floor(x) - 1, 0), min(math.ceil(x + width) + 1, W)
+    r0, r1 = max(math.floor(y) - 1, 0), min(math.ceil(y + height) + 1, H)
+    if c1 <= c0 or r1 <= r0:
+        c1, r1 = c0, r0
+    frames = []
+    if c1 > c0:
+        for fr in li["frames"]:
+            w = fr["window"]
+            if (w["col_off"] < c1 and w["col_off"] + w["width"] > c0 and w["row_off"] < r1
+                    and w["row_off"] + w["height"] > r0):
+                frames.append(fr)
+    return {"level": k, "scale": scale, "out_w": out_w, "out_h": out_h,
+            "window": {"col_off": c0, "row_off": r0, "width": c1 - c0, "height": r1 - r0},
+            "rect": (x - c0, y - r0, width, height), "frames": frames,
+            "transform": [(xmax - xmin) / out_w, 0.0, xmin, 0.0, -(ymax - ymin) / out_h, ymax]}
+
+
+def _index_dtype(src: "Source", index: Dict, index_size: int) -> np.dtype:
+    """The raster dtype, which the index does not carry: from the tags of the file's smallest tile."""
+    frames = [fr for k in overview_levels(index) for fr in level_index(index, k)["frames"]]
+    if not frames:
+        raise ValueError("the streaming index lists no tiles")
+    data = fetch_tiles(src, [min(frames, key=lambda fr: fr["byte_size"])], index_size)[0]
+    md = container.read_raster_tags(container.parse_metadata(data))
+    if md is None:
+        raise ValueError("No metadata found in FLAC file or sidecar file")
+    return np.dtype(md["dtype"])
+
+
+def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, out_h: int,
+                resampling: str = "average", level: Optional[int] = None, fill=0, ctx: Optional[Context] = None):
+    """Extension: bbox = [xmin, ymin, xmax, ymax] of band 1 as exactly out_w x out_h pixels.  window_request picks the
+    overview level and the tiles; they are range-read (fetch_tiles), decoded and placed into the level's pixel window
+    on the device (decode_into_window), resampled there onto the requested grid (frs_resample_window_device, the
+    definition in include/flac_raster_amd.h) and only the out_h x out_w result is downloaded.  Pixels outside the
+    raster get `fill`; a bbox that misses the raster gives an all-`fill` array without a GPU call.  `level` forces
+    the overview level.  Returns (array (1, out_h, out_w), transform list)."""
+    if resampling not in RESAMPLING_READ:
+        raise ValueError(f"resampling must be one of {', '.join(RESAMPLING_READ)}; got {resampling!r}")
+    if not math.isfinite(float(fill)):
+        raise ValueError("fill must be finite")
+    src = Source(flac_url)
+    n, index = read_index(src)
+    req = window_request(index, bbox, out_w, out_h, level)
+    out_w, out_h = req["out_w"], req["out_h"]
+    if not req["frames"]:
+        dtype = _index_dtype(src, index, n)
+        out = np.empty((1, out_h, out_w), dtype=dtype)
+        if dtype.kind == "f":
+            out[...] = fill
+        else:  # the kernel's rule: round half to even, clamp, cast
+            ii = np.iinfo(dtype)
+            out[...] = int(min(max(np.rint(float(fill)), ii.min), ii.max))
+        return out, req["transform"]
+    ctx = ctx or default_context()
+    win = req["window"]
+    datas = fetch_tiles(src, req["frames"], n)
+    wdev, dtype = decode_into_window(datas, req["frames"], (win["col_off"], win["row_off"]),
+                                     (win["height"], win["width"]), ctx)
+    try:
+        dst = ctx.alloc(out_h * out_w * dtype.itemsize)
+    except BaseException:
+        wdev.close()
+        raise
+    try:
+        ctx.resample_window_device(wdev.ptr, ctx.make_raster_desc(win["height"], win["width"], dtype), dst.ptr,
+                                   ctx.make_raster_desc(out_h, out_w, dtype), req["rect"], resampling, fill)
+    except BaseException:
+        dst.close()
+        raise
+    finally:
+        wdev.close()
+    return _download_raster(dst, dtype, out_h, out_w), req["transform"]
+
+
 def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0):
     """Every tile of a streaming file (of overview level `level`) in one batched decode, placed into the level's full
     raster in device memory.  Returns (DeviceBuffer, dtype, level_index(index, level))."""

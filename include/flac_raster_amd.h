@@ -268,11 +268,49 @@ int frs_decode_tiles_window(frs_ctx *ctx, const uint8_t *blob_host, const int64_
  * to the element size, and source and destination byte ranges (origin to the end of the last row) that overlap.
  * Synchronous on the context stream; profile entry "pyramid".  frs_downsample2 takes host rasters: both are copied
  * through the context's staging buffers (the destination goes up first and comes back whole, so its padding survives). */
-enum frs_resample { FRS_RESAMPLE_NEAREST = 0, FRS_RESAMPLE_AVERAGE = 1 };
+/* FRS_RESAMPLE_BILINEAR is frs_resample_window*'s alone: frs_downsample2* reject every mode but 0 and 1 */
+enum frs_resample { FRS_RESAMPLE_NEAREST = 0, FRS_RESAMPLE_AVERAGE = 1, FRS_RESAMPLE_BILINEAR = 2 };
 int frs_downsample2_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev, const frs_raster_desc *dst,
                            void *dst_dev, int32_t mode);
 int frs_downsample2(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
                     void *dst_host, int32_t mode);
+
+/* Resample a rectangle of a raster onto a destination grid of any size: the last stage of a windowed read
+ * (streaming.read_window: "this bounding box as exactly w x h pixels"), so that only the w x h result crosses to the
+ * host.  The reference has no such read.  Both rasters are band-planar [nbands][height][width] elements of the same
+ * dtype (all seven), each with its own row / band stride (frs_raster_desc, nbands 1..8, equal).  The source is H x W,
+ * the destination h x w.  The map's rectangle x0, y0, width, height is in pixel-EDGE coordinates of the source (pixel i
+ * covers [i, i+1)) and may reach outside it.  Per axis, with N the source and n the destination extent:
+ * step = span / n, lo(j) = x0 + j*step, hi(j) = x0 + (j+1)*step, centre(j) = x0 + (j+0.5)*step, each operator one IEEE
+ * fp64 operation (csrc/frs_window_map.h holds the arithmetic for host and device).
+ *   FRS_RESAMPLE_NEAREST    i = floor(centre); the pixel is valid iff 0 <= i < N on both axes
+ *   FRS_RESAMPLE_BILINEAR   valid iff 0 <= floor(centre) < N; u = centre - 0.5, i0 = floor(u), t = u - i0; taps i0 and
+ *                           i0 + 1, each clamped to [0, N-1], weights 1 - t and t; the value is
+ *                           (a(1-tx) + b tx)(1-ty) + (c(1-tx) + d tx) ty with a, b on the upper row
+ *   FRS_RESAMPLE_AVERAGE    clo = max(lo, 0), chi = min(hi, N); valid iff chi > clo on both axes; taps floor(clo) ..
+ *                           ceil(chi) - 1 with weight min(chi, i+1) - max(clo, i); the value is (sum over rows ascending
+ *                           of wy * (sum over columns ascending of wx * v)) / ((chi_x - clo_x)(chi_y - clo_y)), both sums
+ *                           from 0.0.  The tap count is not capped (a 150x reduction reads 150 x 150 taps per pixel).
+ * Source values are converted to double (exact).  Integer results round half to EVEN, are clamped to the dtype's range
+ * and cast (frs_downsample2's integer average rounds half towards +infinity: a different call with a different
+ * definition); float32 narrows the double, float64 keeps it; NaN and +-inf come out as the expression gives them.  A
+ * pixel that is not valid gets map->fill, converted by the same rule; a rectangle wholly outside the source is FRS_OK
+ * and fills the destination.  With x0 = y0 = 0, width = W = w, height = H = h every mode returns a finite source
+ * unchanged.  The definition is this library's own; no parity with GDAL is claimed.
+ * Destination elements outside [h][w] are never written, the row padding of row_stride > width included (whole 16-byte
+ * chunks of a destination row by aligned 16-byte stores, the rest element by element); nothing is read outside the
+ * source's [H][W].  FRS_E_ARG: a size < 1, row_stride < width, nbands outside 1..8 or unequal, dtypes unequal or unknown,
+ * a band_stride (nbands > 1) smaller than (height-1)*row_stride + width, an extent that overflows 63 bits, an unknown
+ * mode, a null pointer or one not aligned to the element size, source and destination byte ranges (origin to the end
+ * of the last row) that overlap, a non-finite map field (fill included), width <= 0 or height <= 0, and a coordinate
+ * (x0, y0, width, height, x0 + width, y0 + height) of magnitude >= 2^52.  Synchronous on the context stream; profile
+ * entry "resample".  frs_resample_window takes host rasters: both are copied through the context's staging buffers (the
+ * destination goes up first and comes back whole, so its padding survives). */
+typedef struct { double x0, y0, width, height, fill; } frs_window_map;
+int frs_resample_window_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                               const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map, int32_t mode);
+int frs_resample_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
+                        void *dst_host, const frs_window_map *map, int32_t mode);
 
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
@@ -313,7 +351,7 @@ int frs_synth_raster_device(frs_ctx *ctx, int16_t *dev, int32_t bands, int64_t h
 void *frs_ctx_stream(frs_ctx *ctx);
 /* Average device time (ms) of the named kernel over the launches since the last reset, measured with
  * HIP events on the context stream (kernel: "encode" = the frame-encode kernel, "analyze", "stats",
- * "compact", "decode", "compare", "place"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
+ * "compact", "decode", "compare", "place", "pyramid", "resample"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
 int frs_profile_enable(frs_ctx *ctx, int on);
 double frs_profile_avg_ms(frs_ctx *ctx, const char *kernel);
 void frs_profile_reset(frs_ctx *ctx);
