@@ -41,6 +41,8 @@ EXPORTS = (
     "frs_place_tiles_device", "frs_decode_tiles_window_device", "frs_decode_tiles_window",
     "frs_downsample2_device", "frs_downsample2",
     "frs_resample_window_device", "frs_resample_window",
+    "frs_downsample2_nodata_device", "frs_downsample2_nodata",
+    "frs_resample_window_nodata_device", "frs_resample_window_nodata",
 )
 
 # enum frs_resample
@@ -258,6 +260,10 @@ def load_library(path: Optional[os.PathLike] = None):
         L.frs_resample_window_device.argtypes = rw_args
         L.frs_resample_window.restype = i32
         L.frs_resample_window.argtypes = rw_args
+        for fn, args in ((L.frs_downsample2_nodata_device, ds_args), (L.frs_downsample2_nodata, ds_args),
+                         (L.frs_resample_window_nodata_device, rw_args), (L.frs_resample_window_nodata, rw_args)):
+            fn.restype = i32
+            fn.argtypes = args + [ctypes.c_double]
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -715,22 +721,27 @@ class Context:
         return int(mode)
 
     def downsample2_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, dst_desc: Optional[RasterDesc] = None,
-                           mode="average") -> RasterDesc:
+                           mode="average", nodata=None) -> RasterDesc:
         """frs_downsample2_device: one 2x step from the device raster at src_ptr (laid out as src_desc) to the one at
         dst_ptr.  dst_desc defaults to the dense ceil(height/2) x ceil(width/2) raster.  `mode` is "average", "nearest"
-        or an enum frs_resample value.  Returns the destination descriptor."""
+        or an enum frs_resample value.  `nodata` (a number): frs_downsample2_nodata_device, the masked step.  Returns
+        the destination descriptor."""
         if dst_desc is None:
             dst_desc = RasterDesc()
             dst_desc.height, dst_desc.width = (src_desc.height + 1) // 2, (src_desc.width + 1) // 2
             dst_desc.row_stride, dst_desc.band_stride = dst_desc.width, dst_desc.width * dst_desc.height
             dst_desc.dtype, dst_desc.nbands = src_desc.dtype, src_desc.nbands
-        self._check(self.lib.frs_downsample2_device(self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr),
-                                                    ctypes.byref(dst_desc), ctypes.c_void_p(dst_ptr),
-                                                    self._resample_code(mode)))
+        args = (self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr), ctypes.byref(dst_desc),
+                ctypes.c_void_p(dst_ptr), self._resample_code(mode))
+        if nodata is None:
+            self._check(self.lib.frs_downsample2_device(*args))
+        else:
+            self._check(self.lib.frs_downsample2_nodata_device(*args, float(nodata)))
         return dst_desc
 
-    def downsample2_host(self, src: np.ndarray, mode="average") -> np.ndarray:
-        """frs_downsample2 on a host raster ((bands, h, w) or (h, w)): the reduced raster, same rank and dtype."""
+    def downsample2_host(self, src: np.ndarray, mode="average", nodata=None) -> np.ndarray:
+        """frs_downsample2 (frs_downsample2_nodata when `nodata` is a number) on a host raster ((bands, h, w) or
+        (h, w)): the reduced raster, same rank and dtype."""
         a = np.ascontiguousarray(src)
         if a.ndim not in (2, 3) or a.dtype not in DTYPE_CODES or a.size == 0:
             raise ValueError("downsample2_host needs a non-empty (bands, h, w) or (h, w) array of a raster dtype")
@@ -739,8 +750,11 @@ class Context:
         sd = self.make_raster_desc(h, w, a.dtype, nbands=nb)
         dd = self.make_raster_desc((h + 1) // 2, (w + 1) // 2, a.dtype, nbands=nb)
         out = np.zeros(((nb,) if a.ndim == 3 else ()) + (dd.height, dd.width), dtype=a.dtype)
-        self._check(self.lib.frs_downsample2(self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out),
-                                             self._resample_code(mode)))
+        args = (self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), self._resample_code(mode))
+        if nodata is None:
+            self._check(self.lib.frs_downsample2(*args))
+        else:
+            self._check(self.lib.frs_downsample2_nodata(*args, float(nodata)))
         return out
 
     # ---- windowed resample
@@ -760,19 +774,25 @@ class Context:
         return WindowMap(x0, y0, width, height, float(fill))
 
     def resample_window_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, dst_desc: RasterDesc, rect,
-                               mode, fill=0) -> None:
+                               mode, fill=0, nodata=None) -> None:
         """frs_resample_window_device: the rectangle rect = (x0, y0, width, height), in pixel-edge coordinates of the
         device raster at src_ptr (laid out as src_desc), resampled onto the whole of the device raster at dst_ptr
         (dst_desc).  `mode` is "nearest", "bilinear", "average" or an enum frs_resample value; destination pixels the
-        source does not cover get `fill`.  `rect` may be a WindowMap, which then carries its own fill."""
+        source does not cover get `fill`.  `rect` may be a WindowMap, which then carries its own fill.  `nodata` (a
+        number): frs_resample_window_nodata_device, which keeps nodata pixels out of every output and gives `fill` to
+        an output without valid weight."""
         m = self._window_map(rect, fill)
-        self._check(self.lib.frs_resample_window_device(self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr),
-                                                        ctypes.byref(dst_desc), ctypes.c_void_p(dst_ptr),
-                                                        ctypes.byref(m), self._window_resample_code(mode)))
+        args = (self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr), ctypes.byref(dst_desc),
+                ctypes.c_void_p(dst_ptr), ctypes.byref(m), self._window_resample_code(mode))
+        if nodata is None:
+            self._check(self.lib.frs_resample_window_device(*args))
+        else:
+            self._check(self.lib.frs_resample_window_nodata_device(*args, float(nodata)))
 
-    def resample_window(self, a: np.ndarray, rect, out_shape, mode="average", fill=0) -> np.ndarray:
-        """frs_resample_window on a host raster ((bands, H, W) or (H, W)): rect = (x0, y0, width, height) of it as an
-        array of out_shape = (h, w) pixels per band, same rank and dtype."""
+    def resample_window(self, a: np.ndarray, rect, out_shape, mode="average", fill=0, nodata=None) -> np.ndarray:
+        """frs_resample_window (frs_resample_window_nodata when `nodata` is a number) on a host raster ((bands, H, W)
+        or (H, W)): rect = (x0, y0, width, height) of it as an array of out_shape = (h, w) pixels per band, same rank
+        and dtype."""
         a = np.ascontiguousarray(a)
         if a.ndim not in (2, 3) or a.dtype not in DTYPE_CODES or a.size == 0:
             raise ValueError("resample_window needs a non-empty (bands, H, W) or (H, W) array of a raster dtype")
@@ -782,8 +802,12 @@ class Context:
         dd = self.make_raster_desc(h, w, a.dtype, nbands=nb)
         out = np.zeros(((nb,) if a.ndim == 3 else ()) + (max(h, 0), max(w, 0)), dtype=a.dtype)
         m = self._window_map(rect, fill)
-        self._check(self.lib.frs_resample_window(self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out),
-                                                 ctypes.byref(m), self._window_resample_code(mode)))
+        args = (self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), ctypes.byref(m),
+                self._window_resample_code(mode))
+        if nodata is None:
+            self._check(self.lib.frs_resample_window(*args))
+        else:
+            self._check(self.lib.frs_resample_window_nodata(*args, float(nodata)))
         return out
 
     # ---- bench helpers

@@ -101,9 +101,20 @@ def create_streaming(
     resampling: str = typer.Option("average", "--resampling", help="Overview resampling: average or nearest"),
     overview_levels: Optional[int] = typer.Option(None, "--overview-levels", min=0,
                                                   help="Write at most N overview levels"),
+    nodata: Optional[str] = typer.Option(None, "--nodata", help="Extension: the value of pixels without data, a number "
+                                                                "or 'source' (the GeoTIFF's own nodata tag): written "
+                                                                "to the index and the tiles, and kept out of the "
+                                                                "overview averages (single GPU only)"),
 ):
     """Create Netflix-style streaming FLAC with self-contained tiles"""
     from . import streaming
+    nd = None
+    if nodata is not None:
+        if gpus > 1 or distributed:
+            typer.echo("Error: --nodata runs on one GPU: it cannot be combined with --gpus > 1 or --distributed",
+                       err=True)
+            raise typer.Exit(1)
+        nd = _nodata_option(nodata, "source")
     # --verify and --overviews are checked before anything else is looked at or done
     if verify and (gpus > 1 or distributed):
         typer.echo("Error: --verify runs on one GPU: it cannot be combined with --gpus > 1 or --distributed", err=True)
@@ -146,12 +157,14 @@ def create_streaming(
             index = create_streaming_distributed(input_file, output_file, tile_size)
         else:
             index = streaming.create_streaming(input_file, output_file, tile_size, overviews=overviews,
-                                               resampling=resampling, max_levels=overview_levels)
+                                               resampling=resampling, max_levels=overview_levels, nodata=nd)
         top = max(streaming.overview_levels(index))
         if overviews:
             typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles, {top} overview levels)")
         else:
             typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles)")
+        if "nodata" in index:
+            typer.echo(f"NODATA: {index['nodata']}")
         if verify:
             from . import geotiff
             ex = streaming.verify_streaming(output_file, geotiff.read(input_file).data[0])
@@ -192,10 +205,14 @@ def extract_streaming(
     resampling: Optional[str] = typer.Option(None, "--resampling",
                                              help="With --out-size: nearest, bilinear or average (default)"),
     fill: Optional[float] = typer.Option(None, "--fill", help="With --out-size: value of pixels outside the raster "
-                                                              "(default 0)"),
+                                                              "(default: the nodata value in force, else 0)"),
+    nodata: Optional[str] = typer.Option(None, "--nodata", help="Extension: override the file's nodata value with a "
+                                                                "number, or 'none' to read without one (default: the "
+                                                                "value in the file's index)"),
 ):
     """Extract tiles from Netflix-style streaming FLAC files"""
     from . import streaming
+    nd = "index" if nodata is None else _nodata_option(nodata, "none")
     # --out-size: every rule is checked before anything is read
     size = None
     if out_size is None and (resampling is not None or fill is not None):
@@ -255,13 +272,14 @@ def extract_streaming(
             _, index = streaming.read_index(flac_url)
             req = streaming.window_request(index, coords, size[0], size[1], level)
             arr, tr = streaming.read_window(flac_url, coords, size[0], size[1], resampling=resampling, level=level,
-                                            fill=0 if fill is None else fill)
+                                            fill=fill, nodata=nd)
             crs = index.get("crs")
             epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
-            geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
+            geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg,
+                          nodata=streaming.nodata_in_force(index, nd))
             typer.echo(f"SUCCESS: window {size[0]}x{size[1]} (level {req['level']}, {resampling}) -> {output}")
         elif all_tiles:
-            index = streaming.extract_all(flac_url, output, level=lvl)
+            index = streaming.extract_all(flac_url, output, level=lvl, nodata=nd)
             typer.echo(f"SUCCESS: Extracted all {len(index['frames'])} tiles to {output}{at}")
         elif mosaic and coords is not None:
             from . import geotiff
@@ -269,11 +287,12 @@ def extract_streaming(
             n, index = streaming.read_index(flac_url)
             crs = index.get("crs")
             epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
-            geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
+            geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg,
+                          nodata=streaming.nodata_in_force(index, nd))
             typer.echo(f"SUCCESS: mosaic {win} -> {output}{at}")
         else:
             f = streaming.extract_streaming(flac_url, output, bbox=coords, tile_id=tile_id, center=center, last=last,
-                                            level=lvl)
+                                            level=lvl, nodata=nd)
             typer.echo(f"SUCCESS: Extracted tile {f['frame_id']} to {output}{at}")
     except (KeyError, LookupError, ValueError) as e:
         typer.echo(f"Error: {e}", err=True)
@@ -281,6 +300,17 @@ def extract_streaming(
     except Exception as e:
         log.exception("Streaming extraction failed")
         typer.echo(f"Error during streaming extraction: {e}", err=True)
+        raise typer.Exit(1)
+
+
+def _nodata_option(text: str, word: str):
+    """--nodata: a number, or the one word the command allows"""
+    if text.strip().lower() == word:
+        return word
+    try:
+        return float(text)
+    except ValueError:
+        typer.echo(f"Error: --nodata must be a number or '{word}', got {text!r}", err=True)
         raise typer.Exit(1)
 
 
@@ -340,6 +370,22 @@ def info(file_path: str = typer.Argument(..., help="FLAC or TIFF file to inspect
             return
         from . import container
         buf = Path(file_path).read_bytes()
+        if buf[:4] != b"fLaC":  # a streaming file starts with its index
+            try:
+                from . import streaming
+                _, index = container.parse_streaming_header(buf)
+                levels = streaming.overview_levels(index)
+                con.print("  Streaming format: Yes")
+                con.print(f"  Dimensions: {index['width']} x {index['height']}")
+                con.print(f"  Tile size: {index['tile_size']}")
+                con.print(f"  Tiles (level 0): {len(index['frames'])}")
+                con.print(f"  Overview levels: {len(levels) - 1}")
+                con.print(f"  CRS: {index.get('crs')}")
+                con.print(f"  Nodata: {index['nodata'] if 'nodata' in index else 'None'}")
+                con.print(f"  File size: {len(buf) / 1024 / 1024:.2f} MB")
+                return
+            except Exception:
+                pass  # not a streaming file either: the messages below
         meta = None
         try:
             import numpy as np

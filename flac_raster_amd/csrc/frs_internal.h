@@ -180,4 +180,9 @@ int place_job(frs_ctx *ctx, const frs_raster_desc *d, const void *tiles_dev, con
 // One 2x reduction step between two device rasters (frs_pyramid.hip); the arguments are already validated.
 int downsample_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d, void *dst_dev,
                    int32_t mode);
+// The same with a nodata value (the masked average of frs_nodata.h; nearest is downsample_job).
+int downsample_nodata_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d,
+                          void *dst_dev, int32_t mode, double nodata);
+// May `nd` be the nodata value of a raster of dtype `dt` (frs_nodata.h: nd_representable)?
+bool nodata_ok(int dt, double nd);
 }  // namespace frs

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "frs_internal.h"
+#include "frs_nodata.h"
 #include "frs_window_map.h"
 
 namespace frs {
@@ -182,6 +183,166 @@ static int window_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_de
     return FRS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The nodata-aware forms (frs_resample_window_nodata*; frs_nodata.h holds the arithmetic).  The mapping and the store
+// side are k_resample_window's; only what a destination row computes per output differs (WinRowNd).
+
+template <int MODE, typename T> struct WinRowNd;
+
+template <typename T> struct WinRowNd<kWindowNearest, T> {
+    const T *s0;
+    T nd;
+    bool valid;
+    __host__ __device__ WinRowNd(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, T nd_) : nd(nd_) {
+        const WinNearest n = win_nearest(ay, r);
+        valid = n.valid, s0 = src + n.i * P.src_row_stride;
+    }
+    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
+        const WinNearest n = win_nearest(ax, x);
+        if (!(valid && n.valid)) return fill;
+        const T v = s0[n.i];
+        return nd_is(v, nd) ? fill : v;
+    }
+};
+
+template <typename T> struct WinRowNd<kWindowBilinear, T> {
+    const T *s0, *s1;
+    double t;
+    T nd;
+    bool valid;
+    __host__ __device__ WinRowNd(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, T nd_) : nd(nd_) {
+        const WinLinear l = win_linear(ay, r);
+        valid = l.valid, t = l.t;
+        s0 = src + l.i0 * P.src_row_stride, s1 = src + l.i1 * P.src_row_stride;
+    }
+    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
+        const WinLinear l = win_linear(ax, x);
+        if (!(valid && l.valid)) return fill;
+        const T a = s0[l.i0], b = s0[l.i1], c = s1[l.i0], d = s1[l.i1];
+        return nd_win_result<T>(nd_bilinear((double)a, (double)b, (double)c, (double)d, !nd_is(a, nd), !nd_is(b, nd),
+                                            !nd_is(c, nd), !nd_is(d, nd), l.t, t),
+                                fill, nd);
+    }
+};
+
+template <typename T> struct WinRowNd<kWindowAverage, T> {
+    const T *src;
+    int64_t row_stride;
+    WinArea ry;
+    T nd;
+    __host__ __device__ WinRowNd(const T *src_, const WinParams &P, const WinAxis &ay, int64_t r, T nd_)
+        : src(src_), row_stride(P.src_row_stride), ry(win_area(ay, r)), nd(nd_) {}
+    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
+        const WinArea rx = win_area(ax, x);
+        if (!(ry.valid && rx.valid)) return fill;
+        NdArea acc;
+        for (int64_t j = ry.i0; j < ry.i1; j++) {
+            const T *s = src + j * row_stride;
+            for (int64_t i = rx.i0; i < rx.i1; i++) {
+                const T v = s[i];
+                acc.tap(win_area_weight(rx, i), (double)v, !nd_is(v, nd));
+            }
+            acc.end_row(win_area_weight(ry, j));
+        }
+        return nd_win_result<T>(acc.value(rx, ry), fill, nd);
+    }
+};
+
+// window_group with a nodata value: the same lanes, chunks and stores.  (Plain C++, as window_group.)
+template <int MODE, typename T>
+__host__ __device__ inline void window_group_nodata(const T *__restrict__ src, T *__restrict__ dst, const WinParams &P,
+                                                    T nd, int64_t bx, int64_t gx, int64_t by, int64_t gy,
+                                                    uint32_t tid) {
+    constexpr int ES = (int)sizeof(T);
+    constexpr int VE = 16 / ES;  // outputs per 16-byte chunk
+    const int64_t w = P.dst_w;
+    const WinAxis ax = win_axis(P.x0, P.width, P.dst_w, P.src_w);
+    const WinAxis ay = win_axis(P.y0, P.height, P.dst_h, P.src_h);
+    const T fill = win_result<T>(P.fill);
+    for (int64_t r = by; r < P.dst_h; r += gy) {
+        const WinRowNd<MODE, T> row(src, P, ay, r, nd);
+        T *d = dst + r * P.dst_row_stride;
+        const int64_t first = (int64_t)(reinterpret_cast<uintptr_t>(d) & 15) / ES;
+        const int64_t cpr = (first + w + VE - 1) / VE;  // chunks the row touches
+        for (int64_t k = bx * kWinBlock + tid; k < cpr; k += gx * kWinBlock) {
+            // chunk k holds the row's outputs [pa, pb)
+            const int64_t p0 = k * VE - first;
+            const int64_t pa = p0 < 0 ? 0 : p0, pb = std::min<int64_t>(p0 + VE, w);
+            T o[VE];
+#pragma unroll
+            for (int e = 0; e < VE; e++) {
+                const int64_t x = p0 + e;
+                o[e] = x >= pa && x < pb ? row.pixel(ax, x, fill) : fill;
+            }
+            if (pb - pa == VE) {  // a whole chunk: d + pa is 16-byte aligned
+                uint4 v;
+                __builtin_memcpy(&v, o, 16);
+                *reinterpret_cast<uint4 *>(d + pa) = v;
+            } else {  // head or tail of the row
+#pragma unroll
+                for (int e = 0; e < VE; e++) {
+                    const int64_t x = p0 + e;
+                    if (x >= pa && x < pb) d[x] = o[e];
+                }
+            }
+        }
+    }
+}
+
+template <int MODE, typename T>
+__global__ void __launch_bounds__(kWinBlock) k_resample_window_nodata(const T *__restrict__ src, T *__restrict__ dst,
+                                                                      WinParams P, T nd) {
+    const int64_t band = blockIdx.z;
+    window_group_nodata<MODE, T>(src + band * P.src_band_stride, dst + band * P.dst_band_stride, P, nd, blockIdx.x,
+                                 gridDim.x, blockIdx.y, gridDim.y, threadIdx.x);
+}
+
+template <typename T>
+static void launch_window_nodata(hipStream_t st, dim3 grid, int32_t mode, const void *src, void *dst,
+                                 const WinParams &P, double nodata) {
+    const T *s = static_cast<const T *>(src);
+    T *d = static_cast<T *>(dst);
+    const T nd = nd_cast<T>(nodata);
+    if (mode == FRS_RESAMPLE_NEAREST)
+        k_resample_window_nodata<kWindowNearest, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd);
+    else if (mode == FRS_RESAMPLE_BILINEAR)
+        k_resample_window_nodata<kWindowBilinear, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd);
+    else
+        k_resample_window_nodata<kWindowAverage, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd);
+}
+
+// window_job with a nodata value (already validated: check_window_nodata below)
+static int window_nodata_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d,
+                             void *dst_dev, const frs_window_map *map, int32_t mode, double nodata) {
+    const int es = dtype_size(d->dtype);
+    WinParams P;
+    P.src_h = s->height, P.src_w = s->width, P.dst_h = d->height, P.dst_w = d->width;
+    P.src_row_stride = s->row_stride, P.src_band_stride = s->band_stride;
+    P.dst_row_stride = d->row_stride, P.dst_band_stride = d->band_stride;
+    P.x0 = map->x0, P.y0 = map->y0, P.width = map->width, P.height = map->height, P.fill = map->fill;
+    // window_job's grid
+    const int64_t cpr = (d->width + 16 / es - 1) / (16 / es) + 1;
+    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(cpr / kWinBlock, 65535));
+    const dim3 grid((unsigned)gx, (unsigned)std::min<int64_t>(d->height, kWinMaxGridY), (unsigned)d->nbands);
+    hipStream_t st = ctx->stream;
+    hipEvent_t ev;
+    prof_begin(ctx, "resample", &ev);
+    switch (d->dtype) {
+    case FRS_DT_U8: launch_window_nodata<uint8_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_U16: launch_window_nodata<uint16_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_I16: launch_window_nodata<int16_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_I32: launch_window_nodata<int32_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_U32: launch_window_nodata<uint32_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_F32: launch_window_nodata<float>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    default: launch_window_nodata<double>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    }
+    prof_end(ctx, "resample", ev);
+    FRS_HIP(hipGetLastError());
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    return FRS_OK;
+}
+
 // elements from a raster's origin to the end of its last row, or -1 when that does not fit 63 bits (with room for the
 // element size)
 static int64_t window_extent(const frs_raster_desc *d) {
@@ -238,6 +399,22 @@ static int check_window_args(frs_ctx *ctx, const frs_raster_desc *src, const frs
     return FRS_OK;
 }
 
+// frs_resample_window_nodata*: the same checks, but a float raster may be filled with NaN, and the nodata value must be
+// one the dtype holds
+static int check_window_nodata_args(frs_ctx *ctx, const frs_raster_desc *src, const frs_raster_desc *dst,
+                                    const frs_window_map *map, int32_t mode, double nodata) {
+    frs_window_map m;
+    const bool nan_fill =
+        map && dst && map->fill != map->fill && (dst->dtype == FRS_DT_F32 || dst->dtype == FRS_DT_F64);
+    if (nan_fill) m = *map, m.fill = 0.0;
+    if (int rc = check_window_args(ctx, src, dst, nan_fill ? &m : map, mode)) return rc;
+    if (!nodata_ok(dst->dtype, nodata)) {
+        ctx->err = "resample: nodata must be an integer inside the dtype's range";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
 static size_t window_bytes(const frs_raster_desc *d) { return (size_t)window_extent(d) * (size_t)dtype_size(d->dtype); }
 
 // null, misaligned or overlapping rasters
@@ -284,6 +461,38 @@ int frs_resample_window(frs_ctx *ctx, const frs_raster_desc *src, const void *sr
     // the destination goes up first: its row and band padding comes back as it was
     FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
     if (int rc = frs::window_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, map, mode)) return rc;
+    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    return FRS_OK;
+}
+
+int frs_resample_window_nodata_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                                      const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map,
+                                      int32_t mode, double nodata) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = frs::check_window_nodata_args(ctx, src, dst, map, mode, nodata)) return rc;
+    if (int rc = frs::check_window_pointers(ctx, src, src_dev, dst, dst_dev)) return rc;
+    FRS_HIP(hipSetDevice(ctx->device));
+    return frs::window_nodata_job(ctx, src, src_dev, dst, dst_dev, map, mode, nodata);
+}
+
+int frs_resample_window_nodata(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host,
+                               const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
+                               double nodata) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = frs::check_window_nodata_args(ctx, src, dst, map, mode, nodata)) return rc;
+    if (int rc = frs::check_window_pointers(ctx, src, src_host, dst, dst_host)) return rc;
+    const size_t sbytes = frs::window_bytes(src), dbytes = frs::window_bytes(dst);
+    FRS_HIP(hipSetDevice(ctx->device));
+    FRS_HIP(ctx->raster_stage.ensure(sbytes));
+    FRS_HIP(ctx->arena_stage.ensure(dbytes));
+    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
+    // the destination goes up first: its row and band padding comes back as it was
+    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = frs::window_nodata_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, map, mode, nodata))
+        return rc;
     FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
     FRS_HIP(hipStreamSynchronize(ctx->stream));
     return FRS_OK;

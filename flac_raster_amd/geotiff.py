@@ -10,6 +10,7 @@ BigTIFF when larger than 4 GB.
 """
 from __future__ import annotations
 
+import math
 import struct
 import zlib
 from dataclasses import dataclass, field
@@ -463,7 +464,9 @@ def write(path, data: np.ndarray, transform: Optional[Affine] = None, epsg: Opti
             gk += list(k)
         add(34735, 3, gk)
     if nodata is not None:
-        add(42113, 2, (repr(float(nodata)) if float(nodata) != int(nodata) else str(int(nodata))).encode() + b"\0")
+        nd = float(nodata)  # ("nan", "inf", "-inf" as GDAL writes them)
+        add(42113, 2, (repr(nd) if nd != nd or nd in (math.inf, -math.inf) or nd != int(nd) else str(int(nd))).encode()
+            + b"\0")
     entries.sort(key=lambda x: x[0])
 
     # layout: header | IFD | out-of-line values | pixel data

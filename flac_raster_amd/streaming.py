@@ -21,6 +21,13 @@ the index gains one key after ``frames``::
 Everything a reader without overview support looks at (the top-level keys, ``frames``) is what it is without them.
 ``level_index`` turns a level into a dict of the top-level index's shape, on which the selection and decode
 functions work unchanged.
+
+Nodata (extension, ``create_streaming*(nodata=V)``): the index gains a top-level ``"nodata": V`` key (NaN and +-inf as
+the JSON strings ``"nan"``, ``"inf"``, ``"-inf"``), every tile's ``GEOSPATIAL_NODATA`` tag carries ``str(float(V))``,
+the overview levels are built with the masked step (frs_downsample2_nodata_device; ``"nodata_aware": true`` in
+``overviews``) and ``read_window`` resamples with the masked kernel, so that a nodata collar or hole is never averaged
+into its neighbours.  Level 0's frames are what they are without nodata.  A file without the key reads exactly as
+before.
 """
 from __future__ import annotations
 
@@ -89,6 +96,34 @@ def level_transform(transform: Sequence[float], level: int) -> List[float]:
     return [a * f, b * f, c, d * f, e * f, f0]
 
 
+def nodata_for_dtype(nd, dtype):
+    """The nodata value `nd` as a raster of `dtype` holds it: a Python int for the integer dtypes, a float (narrowed
+    through float32 for float32) for the float dtypes.  ValueError when an integer dtype cannot hold it: a non-integer
+    value, one outside the dtype's range, NaN or +-inf.  Pure."""
+    dt = np.dtype(dtype)
+    v = float(nd)
+    if dt.kind == "f":
+        with np.errstate(over="ignore"):
+            return float(dt.type(v))
+    if dt.kind not in "iu":
+        raise ValueError(f"nodata: {dt} is not a raster dtype")
+    ii = np.iinfo(dt)
+    if not math.isfinite(v) or v != math.floor(v) or not (ii.min <= v <= ii.max):
+        raise ValueError(f"nodata {nd!r} is not an integer inside the range of {dt} [{ii.min}, {ii.max}]")
+    return int(v)
+
+
+def _nodata_to_index(v):
+    """The index's "nodata" value: the number, or "nan" / "inf" / "-inf" (JSON has no such numbers)."""
+    return v if math.isfinite(v) else str(float(v))
+
+
+def index_nodata(index: Dict) -> Optional[float]:
+    """The nodata value a streaming index carries (its "nodata" key), or None."""
+    v = index.get("nodata")
+    return None if v is None else float(v)
+
+
 def overview_levels(index: Dict) -> List[int]:
     """The levels a streaming index holds: 0 and its overview levels."""
     ov = index.get("overviews") or {}
@@ -98,13 +133,17 @@ def overview_levels(index: Dict) -> List[int]:
 def level_index(index: Dict, level: int = 0) -> Dict:
     """A dict of the streaming index's own shape (crs, transform, width, height, tile_size, frames) for one level;
     level 0 is the index itself.  select_frame, intersecting, first_intersecting, tile_windows and decode_into_window
-    work on the result unchanged.  LookupError (naming the levels present) for a level the file does not hold."""
+    work on the result unchanged.  An index with a "nodata" key passes it on to every level.  LookupError (naming the
+    levels present) for a level the file does not hold."""
     if int(level) == 0:
         return index
     for lv in (index.get("overviews") or {}).get("levels", []):
         if int(lv["level"]) == int(level):
-            return {"crs": index.get("crs"), "transform": list(lv["transform"]), "width": lv["width"],
-                    "height": lv["height"], "tile_size": index.get("tile_size"), "frames": lv["frames"]}
+            li = {"crs": index.get("crs"), "transform": list(lv["transform"]), "width": lv["width"],
+                  "height": lv["height"], "tile_size": index.get("tile_size"), "frames": lv["frames"]}
+            if "nodata" in index:
+                li["nodata"] = index["nodata"]
+            return li
     raise LookupError(f"level {level} not in this file (levels present: {overview_levels(index)})")
 
 
@@ -121,14 +160,15 @@ def pick_level(index: Dict, width_px: int, height_px: int, max_size: int) -> int
     return levels[-1]
 
 
-def tile_tags(crs: Optional[str], tt: geotiff.Affine, w: int, h: int, dtype, tmin: float, tmax: float):
+def tile_tags(crs: Optional[str], tt: geotiff.Affine, w: int, h: int, dtype, tmin: float, tmax: float,
+              nodata: Optional[float] = None):
     """Tags of the per-tile FLAC (tiff_to_flac on the temporary 1-band GeoTIFF, cli.py:719-733)."""
     bounds = geotiff.GeoRaster(np.empty((1, h, w), dtype=np.uint8), tt).bounds
     md = {
         "width": w, "height": h, "count": 1, "dtype": str(np.dtype(dtype)), "crs": crs,
         "transform": list(tt),
         "bounds": {"left": bounds[0], "bottom": bounds[1], "right": bounds[2], "top": bounds[3]},
-        "data_min": tmin, "data_max": tmax, "nodata": None, "driver": "GTiff",
+        "data_min": tmin, "data_max": tmax, "nodata": None if nodata is None else float(nodata), "driver": "GTiff",
     }
     return container.raster_tags(md)
 
@@ -143,14 +183,15 @@ class TileHeaderBuilder:
                ("DESCRIPTION", "TIFF raster converted to FLAC with geospatial metadata"),
                ("ENCODER", "FLAC-Raster v0.1.0"))
 
-    def __init__(self, crs: Optional[str], dtype, stream_bps: int, sample_rate: int = 44100, blocksize: int = 4096):
+    def __init__(self, crs: Optional[str], dtype, stream_bps: int, sample_rate: int = 44100, blocksize: int = 4096,
+                 nodata: Optional[float] = None):
         self._si = container.block(container.BLOCK_STREAMINFO,
                                    container.streaminfo(blocksize, sample_rate, 1, stream_bps), False)
         self._vendor = struct.pack("<I", len(container.VENDOR)) + container.VENDOR + struct.pack("<I", 14)
         ent = self._entry
         self._pre = b"".join(ent(k, v) for k, v in self._PREFIX) + ent("GEOSPATIAL_CRS", str(crs))
         self._mid = (ent("GEOSPATIAL_COUNT", "1") + ent("GEOSPATIAL_DTYPE", str(np.dtype(dtype))) +
-                     ent("GEOSPATIAL_NODATA", "None"))
+                     ent("GEOSPATIAL_NODATA", "None" if nodata is None else str(float(nodata))))
         self._tail = ent("GEOSPATIAL_SPATIAL_TILING", "False")
         self._num: Dict[Tuple[type, object, bool], str] = {}
         self._ent: Dict[Tuple[str, str], bytes] = {}
@@ -222,10 +263,12 @@ def encode_band_tiles(band: np.ndarray, tile_size: int, ctx: Optional[Context] =
 
 
 def streaming_headers(enc: EncodedTiles, transform: geotiff.Affine, crs: Optional[str], width: int, height: int,
-                      tile_size: int, dtype, windows=None, frame_id0: int = 0, byte_offset0: int = 0):
-    """Per-tile headers and index entries of `enc`'s tiles (cli.py:702-759): (headers, frames entries, bytes)."""
+                      tile_size: int, dtype, windows=None, frame_id0: int = 0, byte_offset0: int = 0,
+                      nodata: Optional[float] = None):
+    """Per-tile headers and index entries of `enc`'s tiles (cli.py:702-759): (headers, frames entries, bytes).
+    `nodata` goes into every tile's GEOSPATIAL_NODATA tag."""
     windows = enc.windows if windows is None else windows
-    hb = TileHeaderBuilder(crs, dtype, enc.stream_bps)
+    hb = TileHeaderBuilder(crs, dtype, enc.stream_bps, nodata=nodata)
     headers: List[bytes] = []
     frames: List[Dict] = []
     total = byte_offset0
@@ -313,10 +356,11 @@ def encode_band_tiles_device(ctx: Context, raster_ptr: int, height: int, width: 
 
 def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs: Optional[str], output: Path,
                                 tile_size: int, ctx: Optional[Context], tm: Dict[str, float], resampling: str,
-                                max_levels: Optional[int]) -> Dict:
+                                max_levels: Optional[int], nodata=None) -> Dict:
     """create_streaming_array(overviews=True): the band goes up once; level k is made from level k - 1 on the device
     (frs_downsample2_device) and encoded there like a raster of its own.  Device memory held at any time: the band,
-    two level buffers and one arena (sized for level 0, the largest)."""
+    two level buffers and one arena (sized for level 0, the largest).  With `nodata` (already in the dtype's terms) the
+    step is the masked one."""
     if resampling not in RESAMPLING:
         raise ValueError(f"resampling must be one of {RESAMPLING}, got {resampling!r}")
     ctx = ctx or default_context()
@@ -342,7 +386,7 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
             if k:
                 tp = time.perf_counter()
                 nxt = lv[(k - 1) % 2]
-                cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=resampling)
+                cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=resampling, nodata=nodata)
                 cur = nxt
                 pyr_s += time.perf_counter() - tp
             # level 0 of a large job: frames back into page-locked memory, as without overviews
@@ -361,7 +405,7 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
         lt = level_transform(tr6, k)
         tk = geotiff.Affine(*lt) if k else transform
         headers, frames, nbytes = streaming_headers(enc, tk, crs, w, h, tile_size, dtype, frame_id0=fid,
-                                                    byte_offset0=total)
+                                                    byte_offset0=total, nodata=nodata)
         parts.append((headers, enc, total))
         fid += len(frames)
         total += nbytes
@@ -371,7 +415,12 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
             levels.append({"level": k, "factor": 2 ** k, "width": w, "height": h, "transform": lt,
                            "frames": frames})
     index = {"crs": str(crs), "transform": list(transform), "width": W, "height": H, "tile_size": tile_size,
-             "frames": frames0, "overviews": {"resampling": resampling, "levels": levels}}
+             "frames": frames0}
+    if nodata is not None:
+        index["nodata"] = _nodata_to_index(nodata)
+    index["overviews"] = {"resampling": resampling, "levels": levels}
+    if nodata is not None:
+        index["overviews"]["nodata_aware"] = True
     head = streaming_head(index)
     t2 = time.perf_counter()
     fd = os.open(output, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
@@ -392,22 +441,28 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
 def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Optional[str], output: Path,
                            tile_size: int = 1024, ctx: Optional[Context] = None,
                            timings: Optional[Dict[str, float]] = None, overviews: bool = False,
-                           resampling: str = "average", max_levels: Optional[int] = None) -> Dict:
+                           resampling: str = "average", max_levels: Optional[int] = None, nodata=None) -> Dict:
     """cli.py:620-804 on an in-memory band-1 array: one GPU encode of every tile, headers and index on the host,
     tiles written from the arena with parallel pwritev.  Returns the index; `timings` gets the stage seconds.
     overviews=True (extension) appends reduced-resolution levels (module docstring): `resampling` is "average" or
-    "nearest", `max_levels` caps their number; `timings` then also gets pyramid_s (inside encode_s)."""
+    "nearest", `max_levels` caps their number; `timings` then also gets pyramid_s (inside encode_s).  `nodata`
+    (extension, a number the band's dtype holds: nodata_for_dtype) marks pixels without data (module docstring)."""
     tm = timings if timings is not None else {}
+    if nodata is not None:
+        nodata = nodata_for_dtype(nodata, band.dtype)
     if overviews:
-        return _create_streaming_overviews(band, transform, crs, output, tile_size, ctx, tm, resampling, max_levels)
+        return _create_streaming_overviews(band, transform, crs, output, tile_size, ctx, tm, resampling, max_levels,
+                                           nodata)
     t0 = time.perf_counter()
     H, W = band.shape
     # large jobs: frames back into page-locked memory (DMA rate, no page faults) and written from there
     enc = encode_band_tiles(band, tile_size, ctx, pinned=band.nbytes >= (64 << 20))
     t1 = time.perf_counter()
-    headers, frames, body = streaming_headers(enc, transform, crs, W, H, tile_size, band.dtype)
+    headers, frames, body = streaming_headers(enc, transform, crs, W, H, tile_size, band.dtype, nodata=nodata)
     index = {"crs": str(crs), "transform": list(transform), "width": W, "height": H, "tile_size": tile_size,
              "frames": frames}
+    if nodata is not None:
+        index["nodata"] = _nodata_to_index(nodata)
     head = streaming_head(index)
     t2 = time.perf_counter()
     fd = os.open(output, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
@@ -426,17 +481,24 @@ def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Opt
 def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
                      ctx: Optional[Context] = None, timings: Optional[Dict[str, float]] = None,
                      materialize: bool = False, overviews: bool = False, resampling: str = "average",
-                     max_levels: Optional[int] = None) -> Dict:
+                     max_levels: Optional[int] = None, nodata=None) -> Dict:
     """cli.py:620-804 without the console output: writes the streaming file, returns the index.  Band 1 only
     (cli.py:698-699): an uncompressed band-sequential (or single-band) file is encoded straight from its memory map
     (no host copy of the band); otherwise its strips / tiles are decoded.  `timings` gets read_s + the stages of
     create_streaming_array.  materialize=True reads the band into host memory first (read_s is then the whole read;
     otherwise the band's pages are read while the encode copies them, inside encode_s).  overviews / resampling /
-    max_levels: as create_streaming_array."""
+    max_levels / nodata: as create_streaming_array; nodata="source" takes the GeoTIFF's GDAL_NODATA tag (ValueError
+    when the file has none)."""
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
     with geotiff.TiffFile(input_file) as tf:
-        transform, epsg, _, _ = tf.georef()
+        transform, epsg, src_nodata, _ = tf.georef()
+        if isinstance(nodata, str):
+            if nodata != "source":
+                raise ValueError(f"nodata must be a number or 'source', got {nodata!r}")
+            if src_nodata is None:
+                raise ValueError(f"{input_file} has no GDAL_NODATA tag")
+            nodata = src_nodata
         crs = f"EPSG:{epsg}" if epsg else None
         band = None if materialize else tf.band_view(0)
         if band is None:
@@ -444,7 +506,7 @@ def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
         tm["read_s"] = time.perf_counter() - t0
         transform = transform or geotiff.Affine(1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
         index = create_streaming_array(band, transform, crs, output_file, tile_size, ctx, tm, overviews=overviews,
-                                       resampling=resampling, max_levels=max_levels)
+                                       resampling=resampling, max_levels=max_levels, nodata=nodata)
         del band
     tm["total_s"] = time.perf_counter() - t0
     return index
@@ -649,15 +711,17 @@ def fetch_tiles(src: Union[str, Path, Source], frames: Sequence[Dict], index_siz
 
 def extract_streaming(flac_url: Union[str, Path], output: Path, bbox: Optional[Sequence[float]] = None,
                       tile_id: Optional[int] = None, center: bool = False, last: bool = False,
-                      ctx: Optional[Context] = None, level: int = 0) -> Dict:
+                      ctx: Optional[Context] = None, level: int = 0, nodata="index") -> Dict:
     """cli.py:875-1039: pick one tile, range-read it, decode it and write it as a GeoTIFF.  `level` (extension):
     pick among the tiles of that overview level (tile ids are the level's own frame ids); the GeoTIFF carries the
-    level tile's transform."""
+    level tile's transform.  `nodata` (nodata_in_force): the GeoTIFF's nodata tag is the value in force."""
     src = Source(flac_url)
     n, index = read_index(src)
     f = select_frame(level_index(index, level), tile_id=tile_id, last=last, center=center, bbox=bbox)
     data = fetch_tiles(src, [f], n)[0]
     (arr, md), = TileDecoder(ctx).decode_streams([data])
+    if not (isinstance(nodata, str) and nodata == "index" and "nodata" not in index):  # else: the tile's own tag
+        md = dict(md, nodata=nodata_in_force(index, nodata))
     write_tiff_from_meta(Path(output), arr, md)
     return f
 
@@ -867,30 +931,61 @@ def _index_dtype(src: "Source", index: Dict, index_size: int) -> np.dtype:
     return np.dtype(md["dtype"])
 
 
+def nodata_in_force(index: Dict, nodata="index") -> Optional[float]:
+    """The nodata value a read uses: the index's own ("index", the default), none (None or "none"), or a number that
+    overrides the index."""
+    if nodata is None or (isinstance(nodata, str) and nodata == "none"):
+        return None
+    if isinstance(nodata, str):
+        if nodata != "index":
+            raise ValueError(f"nodata must be a number, None, 'none' or 'index', got {nodata!r}")
+        return index_nodata(index)
+    return float(nodata)
+
+
+def _fill_in_dtype(fill: float, dtype: np.dtype):
+    """`fill` as the resample kernels convert it: integers round half to even, clamp, cast"""
+    if dtype.kind == "f":
+        return fill
+    ii = np.iinfo(dtype)
+    return int(min(max(np.rint(float(fill)), ii.min), ii.max))
+
+
 def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, out_h: int,
-                resampling: str = "average", level: Optional[int] = None, fill=0, ctx: Optional[Context] = None):
+                resampling: str = "average", level: Optional[int] = None, fill=None, ctx: Optional[Context] = None,
+                nodata="index"):
     """Extension: bbox = [xmin, ymin, xmax, ymax] of band 1 as exactly out_w x out_h pixels.  window_request picks the
     overview level and the tiles; they are range-read (fetch_tiles), decoded and placed into the level's pixel window
     on the device (decode_into_window), resampled there onto the requested grid (frs_resample_window_device, the
     definition in include/flac_raster_amd.h) and only the out_h x out_w result is downloaded.  Pixels outside the
     raster get `fill`; a bbox that misses the raster gives an all-`fill` array without a GPU call.  `level` forces
-    the overview level.  Returns (array (1, out_h, out_w), transform list)."""
+    the overview level.  `nodata`: "index" (the default) takes the index's "nodata" key, a number overrides it, None
+    turns masking off; with a value in force the masked kernel runs (frs_resample_window_nodata_device): nodata pixels
+    stay out of every output, and an output with no valid weight gets `fill`.  `fill` defaults to the nodata value in
+    force, else to 0; it must be finite, or NaN for a float raster read with a nodata value.  A file without the key
+    reads exactly as before.  Returns (array (1, out_h, out_w), transform list)."""
     if resampling not in RESAMPLING_READ:
         raise ValueError(f"resampling must be one of {', '.join(RESAMPLING_READ)}; got {resampling!r}")
-    if not math.isfinite(float(fill)):
+    if fill is not None and math.isinf(float(fill)):
         raise ValueError("fill must be finite")
     src = Source(flac_url)
     n, index = read_index(src)
+    nd = nodata_in_force(index, nodata)
+    if fill is None:
+        fill = 0 if nd is None else nd
+    fill = float(fill)
+    if not (math.isfinite(fill) or (nd is not None and math.isnan(fill))):
+        raise ValueError("fill must be finite (or NaN for a float raster read with a nodata value)")
     req = window_request(index, bbox, out_w, out_h, level)
     out_w, out_h = req["out_w"], req["out_h"]
     if not req["frames"]:
         dtype = _index_dtype(src, index, n)
+        if nd is not None:
+            nodata_for_dtype(nd, dtype)
+        if math.isnan(fill) and dtype.kind != "f":
+            raise ValueError("a NaN fill needs a float raster")
         out = np.empty((1, out_h, out_w), dtype=dtype)
-        if dtype.kind == "f":
-            out[...] = fill
-        else:  # the kernel's rule: round half to even, clamp, cast
-            ii = np.iinfo(dtype)
-            out[...] = int(min(max(np.rint(float(fill)), ii.min), ii.max))
+        out[...] = _fill_in_dtype(fill, dtype)  # the kernel's rule
         return out, req["transform"]
     ctx = ctx or default_context()
     win = req["window"]
@@ -903,8 +998,11 @@ def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, o
         wdev.close()
         raise
     try:
+        if nd is not None:
+            nodata_for_dtype(nd, dtype)
         ctx.resample_window_device(wdev.ptr, ctx.make_raster_desc(win["height"], win["width"], dtype), dst.ptr,
-                                   ctx.make_raster_desc(out_h, out_w, dtype), req["rect"], resampling, fill)
+                                   ctx.make_raster_desc(out_h, out_w, dtype), req["rect"], resampling, fill,
+                                   nodata=nd)
     except BaseException:
         dst.close()
         raise
@@ -933,15 +1031,18 @@ def reconstruct(flac_url: Union[str, Path], ctx: Optional[Context] = None, level
     return _download_raster(dst, dtype, int(index["height"]), int(index["width"])), list(index["transform"])
 
 
-def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context] = None, level: int = 0) -> Dict:
+def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context] = None, level: int = 0,
+                nodata="index") -> Dict:
     """extract-streaming --all: write the reconstruction (of overview level `level`) as a GeoTIFF with the index's CRS
-    and the level's transform.  Returns level_index(index, level)."""
+    and the level's transform, and the nodata value in force (nodata_in_force) as its nodata tag.  Returns
+    level_index(index, level)."""
     arr, tr = reconstruct(flac_url, ctx, level)
     _, index = read_index(flac_url)
+    nd = nodata_in_force(index, nodata)
     index = level_index(index, level)
     crs = index.get("crs")
     epsg = int(crs.split(":")[1]) if crs and str(crs).upper().startswith("EPSG:") else None
-    geotiff.write(Path(output), arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg)
+    geotiff.write(Path(output), arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg, nodata=nd)
     return index
 
 
@@ -955,7 +1056,8 @@ def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optiona
     uploaded band with the index's ``resampling`` (frs_downsample2_device, level k from level k - 1) and each decoded
     level is compared with it.  The result then also holds ``levels_checked`` (level 0 included) and ``levels``, one
     dict per level (``level`` + the four keys above); the four top-level keys describe the first level that differs,
-    or level 0 when none does."""
+    or level 0 when none does.  Where the index says ``nodata_aware`` the pyramid is recomputed with the masked step
+    and the index's nodata value."""
     from .compare import _exact
     ctx = ctx or default_context()
     band = np.asarray(band)
@@ -974,6 +1076,9 @@ def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optiona
         if not ov:
             return res
         per_level = [dict(level=0, **res)]
+        nd = index_nodata(index) if ov.get("nodata_aware") else None
+        if ov.get("nodata_aware") and nd is None:
+            raise ValueError("the index says nodata_aware but carries no nodata value")
         cur, cur_desc = srcbuf, ctx.make_raster_desc(H, W, dtype)
         for lv in sorted(ov.get("levels", []), key=lambda x: int(x["level"])):
             k, h, w = int(lv["level"]), (cur_desc.height + 1) // 2, (cur_desc.width + 1) // 2
@@ -981,7 +1086,7 @@ def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optiona
                 raise ValueError(f"overview level {k} is not the 2x reduction of the level before it")
             nxt = ctx.alloc(h * w * dtype.itemsize)
             bufs.append(nxt)
-            cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=ov["resampling"])
+            cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=ov["resampling"], nodata=nd)
             if cur is not srcbuf:
                 cur.close()
             cur = nxt

@@ -312,6 +312,40 @@ int frs_resample_window_device(frs_ctx *ctx, const frs_raster_desc *src, const v
 int frs_resample_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
                         void *dst_host, const frs_window_map *map, int32_t mode);
 
+/* The nodata-aware forms of the two calls above: the same descriptors, validation, synchrony and profile entries
+ * ("pyramid", "resample"), with a trailing nodata value that marks pixels which hold no data.  They keep a nodata
+ * collar or hole from being averaged into its neighbours.  csrc/frs_nodata.h holds the arithmetic for host and device;
+ * the definitions are this library's own, no parity with GDAL is claimed.
+ * Predicate, with ndT = (T)nodata.  Integer dtypes: nodata must be an integer value inside the dtype's range (FRS_E_ARG
+ * otherwise, NaN included); a pixel is nodata iff it equals ndT.  Float dtypes: a pixel is nodata iff it equals ndT or
+ * both are NaN; +-inf is allowed; -0.0 matches 0.0.
+ * frs_downsample2_nodata*, FRS_RESAMPLE_AVERAGE: the block is frs_downsample2's (n = 4, 2 or 1 pixels); its m <= n valid
+ * pixels v1 .. vm are taken in the order a, b, c, d.  m = 0 gives ndT.  Integers: floor((2s + m) / (2m)) of the exact
+ * 64-bit sum s of the valid pixels, the mean rounded half towards +infinity.  Floats: ((v1 + v2) + (v3 + v4)) * 0.25 for
+ * m = 4, ((v1 + v2) + v3) / 3 for m = 3, (v1 + v2) * 0.5 for m = 2, v1 for m = 1, every operation rounded in the dtype.
+ * A block with every pixel valid gives frs_downsample2's result bit for bit, before the nudge: an integer mean (m > 0,
+ * m = n included) that equals ndT becomes ndT + 1, or ndT - 1 when ndT is the dtype's maximum, so that no hole appears
+ * where data exists; floats are not nudged.  FRS_RESAMPLE_NEAREST is frs_downsample2's: the pixel (2r, 2x) is copied, nodata or not.
+ * frs_resample_window_nodata*: indices, weights and axis validity are frs_resample_window's.  An output whose valid
+ * weight is zero (outside the source, all taps nodata, or only zero-weight taps valid) gets map->fill.  Nearest: a
+ * nodata tap gives fill.  Bilinear: with all four taps valid the value is frs_resample_window's; otherwise, with
+ * w00 = (1-tx)(1-ty), w01 = tx(1-ty), w10 = (1-tx)ty, w11 = tx ty and num = den = 0.0, the valid taps are accumulated in
+ * the order 00, 01, 10, 11 (num = num + w v, den = den + w) and the value is num / den, or fill when den == 0.  Average:
+ * per row over its valid taps, columns ascending, row = row + wx v and roww = roww + wx; then, rows ascending,
+ * sum = sum + wy row and wsum = wsum + wy roww; with no tap nodata the value is frs_resample_window's, otherwise
+ * sum / wsum, or fill when wsum == 0.  Integer results are rounded as in frs_resample_window and nudged off ndT as
+ * above.  map->fill must be finite; for float dtypes it may also be NaN. */
+int frs_downsample2_nodata_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                                  const frs_raster_desc *dst, void *dst_dev, int32_t mode, double nodata);
+int frs_downsample2_nodata(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
+                           void *dst_host, int32_t mode, double nodata);
+int frs_resample_window_nodata_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                                      const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map,
+                                      int32_t mode, double nodata);
+int frs_resample_window_nodata(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host,
+                               const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
+                               double nodata);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run

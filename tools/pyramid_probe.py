@@ -14,7 +14,14 @@ End-to-end part (--e2e): streaming.create_streaming_array of a C3 int16 band (de
 into a file under /tmp, without and with overviews, alternated --rounds times in this process after one warm-up of
 each; medians of the wall time and of the stage timings.
 
-usage: pyramid_probe.py [--cases c3,c4,c3_u8,c3_f32] [--reps N] [--warmup N] [--e2e] [--rounds N] [--out PATH]"""
+Nodata part (--nodata, instead of the two above): the C4 level-0 step (40000 x 40000 int16, average) by k_downsample2
+and by k_downsample2_nodata on the same nodata-free band (nodata -9999, which the band does not hold), alternated
+--rounds times in this call, and the masked kernel on the band with about 30 % of its pixels set to -9999.  Written to
+profiles/pyramid_nodata_probe.json with the ratio of the medians (the bar: masked on nodata-free input <= 1.15 x
+unmasked).
+
+usage: pyramid_probe.py [--cases c3,c4,c3_u8,c3_f32] [--reps N] [--warmup N] [--e2e] [--rounds N] [--nodata]
+                        [--out PATH]"""
 import argparse
 import json
 import subprocess
@@ -78,6 +85,58 @@ def kernel_cases(args, out):
     ctx.close()
 
 
+def _timed_step(ctx, args, call):
+    ctx.profile(False)
+    for _ in range(args.warmup):
+        call()
+    ctx.profile(True)
+    ctx.profile_reset()
+    for _ in range(args.reps):
+        call()
+    return ctx.profile_avg_ms("pyramid")
+
+
+def nodata_cases(args, out):
+    from flac_raster_amd import _native
+    ND = -9999
+    ctx = _native.Context(0)
+    dtype, H, W = CASES["c4"]
+    src, holes, dst = ctx.alloc(H * W * 2), ctx.alloc(H * W * 2), ctx.alloc((H // 2) * (W // 2) * 2)
+    ctx.synth_raster(src, 1, H, W, seed=1234)
+    # the same band with ~30 % of its pixels nodata: one random mask of `rows` rows, applied slab by slab
+    rows = 4000
+    mask = np.random.default_rng(7).random((rows, W)) < 0.3
+    slab = np.empty((rows, W), np.int16)
+    for r0 in range(0, H, rows):
+        src.download(slab.nbytes, r0 * W * 2, out=slab.reshape(-1).view(np.uint8))
+        assert not (slab == ND).any()
+        slab[mask] = ND
+        holes.upload(slab, r0 * W * 2)
+    del slab, mask
+    sd = ctx.make_raster_desc(H, W, dtype)
+    moved = H * W * 2 + (H // 2) * (W // 2) * 2
+    runs = {"unmasked": [], "masked_nodata_free": [], "masked_30_percent_nodata": []}
+    for rnd in range(args.rounds):
+        runs["unmasked"].append(_timed_step(ctx, args, lambda: ctx.downsample2_device(src.ptr, sd, dst.ptr)))
+        runs["masked_nodata_free"].append(
+            _timed_step(ctx, args, lambda: ctx.downsample2_device(src.ptr, sd, dst.ptr, nodata=ND)))
+        runs["masked_30_percent_nodata"].append(
+            _timed_step(ctx, args, lambda: ctx.downsample2_device(holes.ptr, sd, dst.ptr, nodata=ND)))
+        print(json.dumps({"round": rnd, **{k: round(v[-1], 4) for k, v in runs.items()}}), flush=True)
+    for b in (src, holes, dst):
+        b.close()
+    ctx.close()
+    med = {k: float(np.median(v)) for k, v in runs.items()}
+    out["nodata"] = {"case": "c4 level-0 step, 40000 x 40000 int16, average", "nodata": ND,
+                     "bytes_read_plus_written": moved, "kernel_ms": {k: [round(x, 4) for x in v] for k, v in runs.items()},
+                     "kernel_ms_median": {k: round(v, 4) for k, v in med.items()},
+                     "fraction_of_achievable": {k: round(moved / (v * 1e-3) / HBM_ACHIEVABLE, 4) for k, v in med.items()},
+                     "masked_nodata_free_over_unmasked": round(med["masked_nodata_free"] / med["unmasked"], 4),
+                     "masked_30_percent_over_unmasked": round(med["masked_30_percent_nodata"] / med["unmasked"], 4),
+                     "bar": 1.15}
+    print(json.dumps(out["nodata"]), flush=True)
+
+
 def end_to_end(args, out):
     from flac_raster_amd import _native, geotiff, streaming
     ctx = _native.Context(0)
@@ -122,16 +181,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--e2e", action="store_true", help="also time create_streaming_array with and without overviews")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "pyramid_probe.json"))
+    ap.add_argument("--nodata", action="store_true",
+                    help="time the masked step beside the unmasked one instead (profiles/pyramid_nodata_probe.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("pyramid_nodata_probe.json" if args.nodata else "pyramid_probe.json"))
     sys.path.insert(0, str(ROOT))
     lib = ROOT / "flac_raster_amd" / "libflac_raster_amd.so"
     sha = subprocess.run(["sha256sum", str(lib)], capture_output=True, text=True).stdout.split()[0][:16]
     out = {"library_sha256_16": sha, "hbm_achievable_bytes_per_s": HBM_ACHIEVABLE, "reps": args.reps,
            "warmup": args.warmup, "tile": TILE, "cases": []}
-    if args.cases:
+    if args.nodata:
+        nodata_cases(args, out)
+    elif args.cases:
         kernel_cases(args, out)
-    if args.e2e:
+    if args.e2e and not args.nodata:
         end_to_end(args, out)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(json.dumps(out, indent=2) + "\n")

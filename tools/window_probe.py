@@ -14,9 +14,14 @@ raster is read with read_window and, for the same bbox, with extract_bbox_mosaic
 caller limited to 256 pixels would have picked by hand; medians of --rounds wall times after one warm-up of each, and
 the bytes each downloads from the device.
 
+Nodata part (--nodata, instead of the two above): 16384^2 -> 8192^2 in each mode by k_resample_window and by
+k_resample_window_nodata on the same nodata-free band (nodata -9999, which the band does not hold), alternated three
+times in this call, and the masked kernel on the band with about 30 % of its pixels set to -9999; medians and ratios,
+written to profiles/window_nodata_probe.json.
+
 Writes profiles/window_probe.json, stamped with the library hash.
 
-usage: window_probe.py [--reps N] [--warmup N] [--e2e] [--rounds N] [--no-kernel] [--out PATH]"""
+usage: window_probe.py [--reps N] [--warmup N] [--e2e] [--rounds N] [--no-kernel] [--nodata] [--out PATH]"""
 import argparse
 import json
 import subprocess
@@ -90,6 +95,45 @@ def kernel_cases(args, out):
     ctx.close()
 
 
+def nodata_cases(args, out):
+    from flac_raster_amd import _native
+    ND = -9999
+    ctx = _native.Context(0)
+    src, holes, half = ctx.alloc(H * W * 2), ctx.alloc(H * W * 2), ctx.alloc((H // 2) * (W // 2) * 2)
+    ctx.synth_raster(src, 1, H, W, seed=1234)
+    rows = 2048  # one random mask of `rows` rows, applied slab by slab
+    mask = np.random.default_rng(7).random((rows, W)) < 0.3
+    slab = np.empty((rows, W), np.int16)
+    for r0 in range(0, H, rows):
+        src.download(slab.nbytes, r0 * W * 2, out=slab.reshape(-1).view(np.uint8))
+        assert not (slab == ND).any()
+        slab[mask] = ND
+        holes.upload(slab, r0 * W * 2)
+    del slab, mask
+    sd = ctx.make_raster_desc(H, W, np.int16)
+    hd = ctx.make_raster_desc(H // 2, W // 2, np.int16)
+    rect = (0.0, 0.0, float(W), float(H))
+    out["nodata"] = {"case": "16384 x 16384 int16 -> 8192 x 8192", "nodata": ND, "modes": {}}
+    for mode in MODES:
+        runs = {"unmasked": [], "masked_nodata_free": [], "masked_30_percent_nodata": []}
+        for _ in range(3):
+            for key, buf, nd in (("unmasked", src, None), ("masked_nodata_free", src, ND),
+                                 ("masked_30_percent_nodata", holes, ND)):
+                ms, _w = _timed(ctx, "resample", args.reps, args.warmup,
+                                lambda: ctx.resample_window_device(buf.ptr, sd, half.ptr, hd, rect, mode, ND, nodata=nd))
+                runs[key].append(ms)
+        med = {k: float(np.median(v)) for k, v in runs.items()}
+        row = {"kernel_ms": {k: [round(x, 4) for x in v] for k, v in runs.items()},
+               "kernel_ms_median": {k: round(v, 4) for k, v in med.items()},
+               "masked_nodata_free_over_unmasked": round(med["masked_nodata_free"] / med["unmasked"], 4),
+               "masked_30_percent_over_unmasked": round(med["masked_30_percent_nodata"] / med["unmasked"], 4)}
+        print(json.dumps({"mode": mode, **row}), flush=True)
+        out["nodata"]["modes"][mode] = row
+    for b in (src, holes, half):
+        b.close()
+    ctx.close()
+
+
 def end_to_end(args, out):
     from flac_raster_amd import _native, geotiff, streaming
     ctx = _native.Context(0)
@@ -142,16 +186,22 @@ def main():
     ap.add_argument("--no-kernel", action="store_true", help="skip the kernel part")
     ap.add_argument("--e2e", action="store_true", help="also time read_window against the mosaic read")
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "window_probe.json"))
+    ap.add_argument("--nodata", action="store_true",
+                    help="time the masked kernel beside the unmasked one instead (profiles/window_nodata_probe.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("window_nodata_probe.json" if args.nodata else "window_probe.json"))
     sys.path.insert(0, str(ROOT))
     lib = ROOT / "flac_raster_amd" / "libflac_raster_amd.so"
     sha = subprocess.run(["sha256sum", str(lib)], capture_output=True, text=True).stdout.split()[0][:16]
     out = {"library_sha256_16": sha, "hbm_achievable_bytes_per_s": HBM_ACHIEVABLE, "reps": args.reps,
            "warmup": args.warmup, "tile": TILE, "cases": []}
-    if not args.no_kernel:
+    if args.nodata:
+        nodata_cases(args, out)
+    elif not args.no_kernel:
         kernel_cases(args, out)
-    if args.e2e:
+    if args.e2e and not args.nodata:
         end_to_end(args, out)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(json.dumps(out, indent=2) + "\n")
