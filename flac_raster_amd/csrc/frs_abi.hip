@@ -822,118 +822,67 @@ bool nodata_ok(int dt, double nd) {
 }
 }  // namespace frs
 
-// frs_downsample2_nodata*: the nodata value must be one the dtype holds
-static int check_downsample_nodata(frs_ctx *ctx, const frs_raster_desc *dst, double nodata) {
-    if (!frs::nodata_ok(dst->dtype, nodata)) {
-        ctx->err = "downsample: nodata must be an integer inside the dtype's range";
-        return FRS_E_ARG;
-    }
-    return FRS_OK;
-}
-
 // bytes from a raster's origin to the end of its last row (the descriptor is already validated)
 static size_t raster_bytes(const frs_raster_desc *d) {
     return (size_t)compare_extent(d->height, d->width, d->nbands, d->row_stride, d->nbands > 1 ? d->band_stride : 0) *
            (size_t)frs::dtype_size(d->dtype);
 }
 
+// null, misaligned or overlapping rasters
+static int check_downsample_pointers(frs_ctx *ctx, const frs_raster_desc *src, const void *sp,
+                                     const frs_raster_desc *dst, const void *dp) {
+    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(sp), b = reinterpret_cast<uintptr_t>(dp);
+    if (!sp || !dp || a % es || b % es) {
+        ctx->err = "downsample: null or element-misaligned pointer";
+        return FRS_E_ARG;
+    }
+    if (a < b + raster_bytes(dst) && b < a + raster_bytes(src)) {
+        ctx->err = "downsample: source and destination overlap";
+        return FRS_E_ARG;
+    }
+    return FRS_OK;
+}
+
+// frs_downsample2*: every check, then the step between the device rasters `sp` / `dp`, or (host) between staged copies
+// of the host rasters they point at.  nodata: null without one; it must be a value the dtype holds.
+static int downsample_entry(frs_ctx *ctx, const frs_raster_desc *src, const void *sp, const frs_raster_desc *dst,
+                            void *dp, int32_t mode, const double *nodata, bool host) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = frs::check_unsynced(ctx)) return rc;
+    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
+    if (nodata && !frs::nodata_ok(dst->dtype, *nodata)) {
+        ctx->err = "downsample: nodata must be an integer inside the dtype's range";
+        return FRS_E_ARG;
+    }
+    if (int rc = check_downsample_pointers(ctx, src, sp, dst, dp)) return rc;
+    FRS_HIP(hipSetDevice(ctx->device));
+    if (!host) return frs::downsample_job(ctx, src, sp, dst, dp, mode, nodata);
+    return frs::run_staged(ctx, sp, raster_bytes(src), dp, raster_bytes(dst), [&](const void *src_dev, void *dst_dev) {
+        return frs::downsample_job(ctx, src, src_dev, dst, dst_dev, mode, nodata);
+    });
+}
+
 extern "C" {
 
 int frs_downsample2_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev, const frs_raster_desc *dst,
                            void *dst_dev, int32_t mode) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
-    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src_dev), b = reinterpret_cast<uintptr_t>(dst_dev);
-    if (!src_dev || !dst_dev || a % es || b % es) {
-        ctx->err = "downsample: null or element-misaligned pointer";
-        return FRS_E_ARG;
-    }
-    if (a < b + raster_bytes(dst) && b < a + raster_bytes(src)) {
-        ctx->err = "downsample: source and destination overlap";
-        return FRS_E_ARG;
-    }
-    FRS_HIP(hipSetDevice(ctx->device));
-    return frs::downsample_job(ctx, src, src_dev, dst, dst_dev, mode);
+    return downsample_entry(ctx, src, src_dev, dst, dst_dev, mode, nullptr, false);
 }
 
 int frs_downsample2(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
                     void *dst_host, int32_t mode) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
-    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src_host), b = reinterpret_cast<uintptr_t>(dst_host);
-    if (!src_host || !dst_host || a % es || b % es) {
-        ctx->err = "downsample: null or element-misaligned pointer";
-        return FRS_E_ARG;
-    }
-    const size_t sbytes = raster_bytes(src), dbytes = raster_bytes(dst);
-    if (a < b + dbytes && b < a + sbytes) {
-        ctx->err = "downsample: source and destination overlap";
-        return FRS_E_ARG;
-    }
-    FRS_HIP(hipSetDevice(ctx->device));
-    FRS_HIP(ctx->raster_stage.ensure(sbytes));
-    FRS_HIP(ctx->arena_stage.ensure(dbytes));
-    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
-    // the destination goes up first: its row and band padding comes back as it was
-    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = frs::downsample_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, mode)) return rc;
-    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
-    FRS_HIP(hipStreamSynchronize(ctx->stream));
-    return FRS_OK;
+    return downsample_entry(ctx, src, src_host, dst, dst_host, mode, nullptr, true);
 }
 
 int frs_downsample2_nodata_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
                                   const frs_raster_desc *dst, void *dst_dev, int32_t mode, double nodata) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
-    if (int rc = check_downsample_nodata(ctx, dst, nodata)) return rc;
-    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src_dev), b = reinterpret_cast<uintptr_t>(dst_dev);
-    if (!src_dev || !dst_dev || a % es || b % es) {
-        ctx->err = "downsample: null or element-misaligned pointer";
-        return FRS_E_ARG;
-    }
-    if (a < b + raster_bytes(dst) && b < a + raster_bytes(src)) {
-        ctx->err = "downsample: source and destination overlap";
-        return FRS_E_ARG;
-    }
-    FRS_HIP(hipSetDevice(ctx->device));
-    return frs::downsample_nodata_job(ctx, src, src_dev, dst, dst_dev, mode, nodata);
+    return downsample_entry(ctx, src, src_dev, dst, dst_dev, mode, &nodata, false);
 }
 
 int frs_downsample2_nodata(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
                            void *dst_host, int32_t mode, double nodata) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = check_downsample_args(ctx, src, dst, mode)) return rc;
-    if (int rc = check_downsample_nodata(ctx, dst, nodata)) return rc;
-    const uintptr_t es = (uintptr_t)frs::dtype_size(dst->dtype);
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src_host), b = reinterpret_cast<uintptr_t>(dst_host);
-    if (!src_host || !dst_host || a % es || b % es) {
-        ctx->err = "downsample: null or element-misaligned pointer";
-        return FRS_E_ARG;
-    }
-    const size_t sbytes = raster_bytes(src), dbytes = raster_bytes(dst);
-    if (a < b + dbytes && b < a + sbytes) {
-        ctx->err = "downsample: source and destination overlap";
-        return FRS_E_ARG;
-    }
-    FRS_HIP(hipSetDevice(ctx->device));
-    FRS_HIP(ctx->raster_stage.ensure(sbytes));
-    FRS_HIP(ctx->arena_stage.ensure(dbytes));
-    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
-    // the destination goes up first: its row and band padding comes back as it was
-    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = frs::downsample_nodata_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, mode, nodata))
-        return rc;
-    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
-    FRS_HIP(hipStreamSynchronize(ctx->stream));
-    return FRS_OK;
+    return downsample_entry(ctx, src, src_host, dst, dst_host, mode, &nodata, true);
 }
 
 }  // extern "C"

@@ -177,12 +177,25 @@ int compare_job(frs_ctx *ctx, const frs_compare_desc *d, const void *a_dev, cons
 // Place ntiles decoded tiles into a device raster (frs_place.hip); the arguments are already validated.
 int place_job(frs_ctx *ctx, const frs_raster_desc *d, const void *tiles_dev, const int64_t *pcm_off,
               const frs_tile_window *win, int32_t ntiles, void *dst_dev);
-// One 2x reduction step between two device rasters (frs_pyramid.hip); the arguments are already validated.
-int downsample_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d, void *dst_dev,
-                   int32_t mode);
-// The same with a nodata value (the masked average of frs_nodata.h; nearest is downsample_job).
-int downsample_nodata_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d,
-                          void *dst_dev, int32_t mode, double nodata);
+// One 2x reduction step between two device rasters (frs_pyramid.hip); the arguments are already validated.  `nodata`
+// is null, or points at the nodata value (the masked average of frs_nodata.h; nearest is the same with and without).
+int downsample_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src, const frs_raster_desc *d, void *dst,
+                   int32_t mode, const double *nodata);
 // May `nd` be the nodata value of a raster of dtype `dt` (frs_nodata.h: nd_representable)?
 bool nodata_ok(int dt, double nd);
+
+// The host-pointer form of a job between two rasters (frs_downsample2*, frs_resample_window*): both rasters go up to
+// the context's staging buffers, job(src_dev, dst_dev) runs on them, the destination comes back.
+template <typename Job>
+int run_staged(frs_ctx *ctx, const void *src_host, size_t sbytes, void *dst_host, size_t dbytes, Job job) {
+    FRS_HIP(ctx->raster_stage.ensure(sbytes));
+    FRS_HIP(ctx->arena_stage.ensure(dbytes));
+    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
+    // the destination goes up first: its row and band padding comes back as it was
+    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = job(ctx->raster_stage.ptr, ctx->arena_stage.ptr)) return rc;
+    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
+    FRS_HIP(hipStreamSynchronize(ctx->stream));
+    return FRS_OK;
+}
 }  // namespace frs

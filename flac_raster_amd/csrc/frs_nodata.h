@@ -3,8 +3,8 @@
 // HIP, only the two headers whose arithmetic it extends: a plain C++ compiler builds it (tests/test_nodata_host.py
 // compares it with exact integers and with the numpy restatement in tests/nodata_ref.py, bit for bit), hipcc builds the
 // same text as __host__ __device__.  Needs -ffp-contract=off like the rest of the library: every operator below is one
-// IEEE operation.  Users: downsample_group_nodata in frs_pyramid.hip and window_group_nodata in frs_window.hip, which
-// keep their own loads, stores and loops.
+// IEEE operation.  Users: downsample_group in frs_pyramid.hip and window_group in frs_window.hip under their Nodata<T>
+// policy (at the end of this file); they keep their own loads, stores and loops.
 //
 // The definitions are the project's own (no parity with GDAL's or any other library's masked resampling is claimed).
 //
@@ -165,5 +165,15 @@ struct NdArea {
 template <typename T> FRS_HD inline T nd_win_result(const NdValue &r, T fill, T nd) {
     return r.valid ? nd_nudge(win_result<T>(r.v), nd) : fill;
 }
+
+// The mask policy of the lane functions (downsample_group, window_group): NoNodata compiles the forms of
+// frs_resample.h / frs_window_map.h alone, Nodata<T> the forms above with nd = ndT.
+struct NoNodata {
+    static constexpr bool masked = false;
+};
+template <typename T> struct Nodata {
+    static constexpr bool masked = true;
+    T nd;
+};
 
 }  // namespace frs

@@ -1,16 +1,21 @@
 // frs_window.hip -- resample a rectangle of a band-planar raster onto a destination grid of any size
-// (frs_resample_window*), by the arithmetic of frs_window_map.h (nearest, bilinear, or the area-weighted average).
+// (frs_resample_window*), by the arithmetic of frs_window_map.h (nearest, bilinear, or the area-weighted average) and,
+// with a nodata value, of frs_nodata.h (nodata taps left out of an output, an output without a valid tap filled).
 //
 // There is no reference path: the reference reads whole tiles at the one resolution a file holds.  It is the last
 // stage of streaming.read_window: the tiles a bounding box needs are decoded and placed into a device window
 // (frs_decode_tiles_window_device), this kernel maps the box onto the W x H pixels the caller asked for, and only those
 // cross to the host.
 //
-//   k_resample_window   grid (gx, gy, nbands), 256 threads.  Work-group (bx, by, band) owns destination rows by,
-//                       by + gy, ... of the band and, of each, the 16-byte chunks bx * 256 + lane, striding gx * 256.
-//                       Row and band come from the block index alone: the row's taps, weights and validity
-//                       (win_nearest / win_linear / win_area of the y axis), the source row pointers and the row's
-//                       alignment are uniform over the work-group.
+//   k_resample_window          grid (gx, gy, nbands), 256 threads.  Work-group (bx, by, band) owns destination rows
+//   k_resample_window_nodata   by, by + gy, ... of the band and, of each, the 16-byte chunks bx * 256 + lane, striding
+//                              gx * 256.  Row and band come from the block index alone: the row's taps, weights and
+//                              validity (win_nearest / win_linear / win_area of the y axis), the source row pointers
+//                              and the row's alignment are uniform over the work-group.
+//
+// Both kernels are one lane function, window_group, with a mask policy (frs_nodata.h): NoNodata, or Nodata<T> with the
+// nodata value.  The policy reaches only WinRow::pixel, what one output is computed from its taps; the mapping, the
+// chunks and the stores do not know of it.
 //
 // Store side, as in frs_place.hip and frs_pyramid.hip: a destination row is cut at the 16-byte boundaries of the
 // DESTINATION; a chunk that lies wholly inside the row leaves as one aligned 16-byte store per lane, the first and last
@@ -21,8 +26,8 @@
 // inside [0, N): nothing is read outside the source's [H][W].  The average's tap loops are not capped (a 150x reduction
 // reads 150 x 150 taps per output).  No LDS, no atomics, no init pass.
 //
-// One instantiation per (dtype, mode): the conversion to double and the rounding differ per dtype, and there is no
-// per-element switch on either.
+// One instantiation per (dtype, mode, policy): the conversion to double and the rounding differ per dtype, and there
+// is no per-element switch on any of the three.
 #include <algorithm>
 
 #include "frs_internal.h"
@@ -40,27 +45,38 @@ struct WinParams {
     double x0, y0, width, height, fill;
 };
 
-// What a destination row needs of the y axis, and one output of that row.
-template <int MODE, typename T> struct WinRow;
+// What a destination row needs of the y axis, and one output of that row.  `mask` is NoNodata, or Nodata<T>: then a
+// nodata tap is left out of the output, and an output without a valid tap is `fill`.
+template <int MODE, typename T, typename Mask> struct WinRow;
 
-template <typename T> struct WinRow<kWindowNearest, T> {
+template <typename T, typename Mask> struct WinRow<kWindowNearest, T, Mask> {
     const T *s0;
     bool valid;
-    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r) {
+    Mask mask;
+    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, const Mask &mask_)
+        : mask(mask_) {
         const WinNearest n = win_nearest(ay, r);
         valid = n.valid, s0 = src + n.i * P.src_row_stride;
     }
     __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
         const WinNearest n = win_nearest(ax, x);
-        return valid && n.valid ? s0[n.i] : fill;
+        if constexpr (Mask::masked) {
+            if (!(valid && n.valid)) return fill;
+            const T v = s0[n.i];
+            return nd_is(v, mask.nd) ? fill : v;
+        } else {
+            return valid && n.valid ? s0[n.i] : fill;
+        }
     }
 };
 
-template <typename T> struct WinRow<kWindowBilinear, T> {
+template <typename T, typename Mask> struct WinRow<kWindowBilinear, T, Mask> {
     const T *s0, *s1;
     double t;
     bool valid;
-    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r) {
+    Mask mask;
+    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, const Mask &mask_)
+        : mask(mask_) {
         const WinLinear l = win_linear(ay, r);
         valid = l.valid, t = l.t;
         s0 = src + l.i0 * P.src_row_stride, s1 = src + l.i1 * P.src_row_stride;
@@ -68,36 +84,58 @@ template <typename T> struct WinRow<kWindowBilinear, T> {
     __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
         const WinLinear l = win_linear(ax, x);
         if (!(valid && l.valid)) return fill;
-        const double a = (double)s0[l.i0], b = (double)s0[l.i1], c = (double)s1[l.i0], d = (double)s1[l.i1];
-        return win_result<T>(win_bilinear_value(a, b, c, d, l.t, t));
+        if constexpr (Mask::masked) {
+            const T a = s0[l.i0], b = s0[l.i1], c = s1[l.i0], d = s1[l.i1], nd = mask.nd;
+            return nd_win_result<T>(nd_bilinear((double)a, (double)b, (double)c, (double)d, !nd_is(a, nd),
+                                                !nd_is(b, nd), !nd_is(c, nd), !nd_is(d, nd), l.t, t),
+                                    fill, nd);
+        } else {
+            const double a = (double)s0[l.i0], b = (double)s0[l.i1], c = (double)s1[l.i0], d = (double)s1[l.i1];
+            return win_result<T>(win_bilinear_value(a, b, c, d, l.t, t));
+        }
     }
 };
 
-template <typename T> struct WinRow<kWindowAverage, T> {
+template <typename T, typename Mask> struct WinRow<kWindowAverage, T, Mask> {
     const T *src;
     int64_t row_stride;
     WinArea ry;
-    __host__ __device__ WinRow(const T *src_, const WinParams &P, const WinAxis &ay, int64_t r)
-        : src(src_), row_stride(P.src_row_stride), ry(win_area(ay, r)) {}
+    Mask mask;
+    __host__ __device__ WinRow(const T *src_, const WinParams &P, const WinAxis &ay, int64_t r, const Mask &mask_)
+        : src(src_), row_stride(P.src_row_stride), ry(win_area(ay, r)), mask(mask_) {}
     __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
         const WinArea rx = win_area(ax, x);
         if (!(ry.valid && rx.valid)) return fill;
-        double sum = 0.0;
-        for (int64_t j = ry.i0; j < ry.i1; j++) {
-            const T *s = src + j * row_stride;
-            double row = 0.0;
-            for (int64_t i = rx.i0; i < rx.i1; i++) row = row + win_area_weight(rx, i) * (double)s[i];
-            sum = sum + win_area_weight(ry, j) * row;
+        if constexpr (Mask::masked) {
+            NdArea acc;
+            for (int64_t j = ry.i0; j < ry.i1; j++) {
+                const T *s = src + j * row_stride;
+                for (int64_t i = rx.i0; i < rx.i1; i++) {
+                    const T v = s[i];
+                    acc.tap(win_area_weight(rx, i), (double)v, !nd_is(v, mask.nd));
+                }
+                acc.end_row(win_area_weight(ry, j));
+            }
+            return nd_win_result<T>(acc.value(rx, ry), fill, mask.nd);
+        } else {
+            double sum = 0.0;
+            for (int64_t j = ry.i0; j < ry.i1; j++) {
+                const T *s = src + j * row_stride;
+                double row = 0.0;
+                for (int64_t i = rx.i0; i < rx.i1; i++) row = row + win_area_weight(rx, i) * (double)s[i];
+                sum = sum + win_area_weight(ry, j) * row;
+            }
+            return win_result<T>(win_area_value(sum, rx, ry));
         }
-        return win_result<T>(win_area_value(sum, rx, ry));
     }
 };
 
 // One lane's share of a work-group: lane tid of work-group (bx of gx, by of gy) of one band (src / dst are the band's
 // origins).  (Plain C++, so that a host program can run it lane by lane against a direct evaluation.)
-template <int MODE, typename T>
+template <int MODE, typename T, typename Mask>
 __host__ __device__ inline void window_group(const T *__restrict__ src, T *__restrict__ dst, const WinParams &P,
-                                             int64_t bx, int64_t gx, int64_t by, int64_t gy, uint32_t tid) {
+                                             const Mask &mask, int64_t bx, int64_t gx, int64_t by, int64_t gy,
+                                             uint32_t tid) {
     constexpr int ES = (int)sizeof(T);
     constexpr int VE = 16 / ES;  // outputs per 16-byte chunk
     const int64_t w = P.dst_w;
@@ -105,7 +143,7 @@ __host__ __device__ inline void window_group(const T *__restrict__ src, T *__res
     const WinAxis ay = win_axis(P.y0, P.height, P.dst_h, P.src_h);
     const T fill = win_result<T>(P.fill);
     for (int64_t r = by; r < P.dst_h; r += gy) {
-        const WinRow<MODE, T> row(src, P, ay, r);
+        const WinRow<MODE, T, Mask> row(src, P, ay, r, mask);
         T *d = dst + r * P.dst_row_stride;
         const int64_t first = (int64_t)(reinterpret_cast<uintptr_t>(d) & 15) / ES;
         const int64_t cpr = (first + w + VE - 1) / VE;  // chunks the row touches
@@ -134,26 +172,45 @@ __host__ __device__ inline void window_group(const T *__restrict__ src, T *__res
     }
 }
 
+// The two kernels differ in their arguments alone.
 template <int MODE, typename T>
 __global__ void __launch_bounds__(kWinBlock) k_resample_window(const T *__restrict__ src, T *__restrict__ dst,
                                                                WinParams P) {
     const int64_t band = blockIdx.z;
-    window_group<MODE, T>(src + band * P.src_band_stride, dst + band * P.dst_band_stride, P, blockIdx.x, gridDim.x,
-                          blockIdx.y, gridDim.y, threadIdx.x);
+    window_group<MODE, T>(src + band * P.src_band_stride, dst + band * P.dst_band_stride, P, NoNodata{}, blockIdx.x,
+                          gridDim.x, blockIdx.y, gridDim.y, threadIdx.x);
+}
+
+template <int MODE, typename T>
+__global__ void __launch_bounds__(kWinBlock) k_resample_window_nodata(const T *__restrict__ src, T *__restrict__ dst,
+                                                                      WinParams P, T nd) {
+    const int64_t band = blockIdx.z;
+    window_group<MODE, T>(src + band * P.src_band_stride, dst + band * P.dst_band_stride, P, Nodata<T>{nd},
+                          blockIdx.x, gridDim.x, blockIdx.y, gridDim.y, threadIdx.x);
+}
+
+// nodata: null without one
+template <int MODE, typename T>
+static void launch_window_mode(hipStream_t st, dim3 grid, const void *src, void *dst, const WinParams &P,
+                               const double *nodata) {
+    const T *s = static_cast<const T *>(src);
+    T *d = static_cast<T *>(dst);
+    if (nodata) k_resample_window_nodata<MODE, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd_cast<T>(*nodata));
+    else k_resample_window<MODE, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
 }
 
 template <typename T>
-static void launch_window(hipStream_t st, dim3 grid, int32_t mode, const void *src, void *dst, const WinParams &P) {
-    const T *s = static_cast<const T *>(src);
-    T *d = static_cast<T *>(dst);
-    if (mode == FRS_RESAMPLE_NEAREST) k_resample_window<kWindowNearest, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
-    else if (mode == FRS_RESAMPLE_BILINEAR) k_resample_window<kWindowBilinear, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
-    else k_resample_window<kWindowAverage, T><<<grid, kWinBlock, 0, st>>>(s, d, P);
+static void launch_window(hipStream_t st, dim3 grid, int32_t mode, const void *src, void *dst, const WinParams &P,
+                          const double *nodata) {
+    if (mode == FRS_RESAMPLE_NEAREST) launch_window_mode<kWindowNearest, T>(st, grid, src, dst, P, nodata);
+    else if (mode == FRS_RESAMPLE_BILINEAR) launch_window_mode<kWindowBilinear, T>(st, grid, src, dst, P, nodata);
+    else launch_window_mode<kWindowAverage, T>(st, grid, src, dst, P, nodata);
 }
 
-// The arguments are already validated (check_window_args below).  Synchronous on the context stream.
+// The arguments are already validated (window_entry below), the nodata value for the dtype as well (null: none).
+// Synchronous on the context stream.
 static int window_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d,
-                      void *dst_dev, const frs_window_map *map, int32_t mode) {
+                      void *dst_dev, const frs_window_map *map, int32_t mode, const double *nodata) {
     const int es = dtype_size(d->dtype);
     WinParams P;
     P.src_h = s->height, P.src_w = s->width, P.dst_h = d->height, P.dst_w = d->width;
@@ -168,173 +225,13 @@ static int window_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_de
     hipEvent_t ev;
     prof_begin(ctx, "resample", &ev);
     switch (d->dtype) {
-    case FRS_DT_U8: launch_window<uint8_t>(st, grid, mode, src_dev, dst_dev, P); break;
-    case FRS_DT_U16: launch_window<uint16_t>(st, grid, mode, src_dev, dst_dev, P); break;
-    case FRS_DT_I16: launch_window<int16_t>(st, grid, mode, src_dev, dst_dev, P); break;
-    case FRS_DT_I32: launch_window<int32_t>(st, grid, mode, src_dev, dst_dev, P); break;
-    case FRS_DT_U32: launch_window<uint32_t>(st, grid, mode, src_dev, dst_dev, P); break;
-    case FRS_DT_F32: launch_window<float>(st, grid, mode, src_dev, dst_dev, P); break;
-    default: launch_window<double>(st, grid, mode, src_dev, dst_dev, P); break;
-    }
-    prof_end(ctx, "resample", ev);
-    FRS_HIP(hipGetLastError());
-    FRS_HIP(hipStreamSynchronize(ctx->stream));
-    prof_collect(ctx);
-    return FRS_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The nodata-aware forms (frs_resample_window_nodata*; frs_nodata.h holds the arithmetic).  The mapping and the store
-// side are k_resample_window's; only what a destination row computes per output differs (WinRowNd).
-
-template <int MODE, typename T> struct WinRowNd;
-
-template <typename T> struct WinRowNd<kWindowNearest, T> {
-    const T *s0;
-    T nd;
-    bool valid;
-    __host__ __device__ WinRowNd(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, T nd_) : nd(nd_) {
-        const WinNearest n = win_nearest(ay, r);
-        valid = n.valid, s0 = src + n.i * P.src_row_stride;
-    }
-    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
-        const WinNearest n = win_nearest(ax, x);
-        if (!(valid && n.valid)) return fill;
-        const T v = s0[n.i];
-        return nd_is(v, nd) ? fill : v;
-    }
-};
-
-template <typename T> struct WinRowNd<kWindowBilinear, T> {
-    const T *s0, *s1;
-    double t;
-    T nd;
-    bool valid;
-    __host__ __device__ WinRowNd(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, T nd_) : nd(nd_) {
-        const WinLinear l = win_linear(ay, r);
-        valid = l.valid, t = l.t;
-        s0 = src + l.i0 * P.src_row_stride, s1 = src + l.i1 * P.src_row_stride;
-    }
-    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
-        const WinLinear l = win_linear(ax, x);
-        if (!(valid && l.valid)) return fill;
-        const T a = s0[l.i0], b = s0[l.i1], c = s1[l.i0], d = s1[l.i1];
-        return nd_win_result<T>(nd_bilinear((double)a, (double)b, (double)c, (double)d, !nd_is(a, nd), !nd_is(b, nd),
-                                            !nd_is(c, nd), !nd_is(d, nd), l.t, t),
-                                fill, nd);
-    }
-};
-
-template <typename T> struct WinRowNd<kWindowAverage, T> {
-    const T *src;
-    int64_t row_stride;
-    WinArea ry;
-    T nd;
-    __host__ __device__ WinRowNd(const T *src_, const WinParams &P, const WinAxis &ay, int64_t r, T nd_)
-        : src(src_), row_stride(P.src_row_stride), ry(win_area(ay, r)), nd(nd_) {}
-    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
-        const WinArea rx = win_area(ax, x);
-        if (!(ry.valid && rx.valid)) return fill;
-        NdArea acc;
-        for (int64_t j = ry.i0; j < ry.i1; j++) {
-            const T *s = src + j * row_stride;
-            for (int64_t i = rx.i0; i < rx.i1; i++) {
-                const T v = s[i];
-                acc.tap(win_area_weight(rx, i), (double)v, !nd_is(v, nd));
-            }
-            acc.end_row(win_area_weight(ry, j));
-        }
-        return nd_win_result<T>(acc.value(rx, ry), fill, nd);
-    }
-};
-
-// window_group with a nodata value: the same lanes, chunks and stores.  (Plain C++, as window_group.)
-template <int MODE, typename T>
-__host__ __device__ inline void window_group_nodata(const T *__restrict__ src, T *__restrict__ dst, const WinParams &P,
-                                                    T nd, int64_t bx, int64_t gx, int64_t by, int64_t gy,
-                                                    uint32_t tid) {
-    constexpr int ES = (int)sizeof(T);
-    constexpr int VE = 16 / ES;  // outputs per 16-byte chunk
-    const int64_t w = P.dst_w;
-    const WinAxis ax = win_axis(P.x0, P.width, P.dst_w, P.src_w);
-    const WinAxis ay = win_axis(P.y0, P.height, P.dst_h, P.src_h);
-    const T fill = win_result<T>(P.fill);
-    for (int64_t r = by; r < P.dst_h; r += gy) {
-        const WinRowNd<MODE, T> row(src, P, ay, r, nd);
-        T *d = dst + r * P.dst_row_stride;
-        const int64_t first = (int64_t)(reinterpret_cast<uintptr_t>(d) & 15) / ES;
-        const int64_t cpr = (first + w + VE - 1) / VE;  // chunks the row touches
-        for (int64_t k = bx * kWinBlock + tid; k < cpr; k += gx * kWinBlock) {
-            // chunk k holds the row's outputs [pa, pb)
-            const int64_t p0 = k * VE - first;
-            const int64_t pa = p0 < 0 ? 0 : p0, pb = std::min<int64_t>(p0 + VE, w);
-            T o[VE];
-#pragma unroll
-            for (int e = 0; e < VE; e++) {
-                const int64_t x = p0 + e;
-                o[e] = x >= pa && x < pb ? row.pixel(ax, x, fill) : fill;
-            }
-            if (pb - pa == VE) {  // a whole chunk: d + pa is 16-byte aligned
-                uint4 v;
-                __builtin_memcpy(&v, o, 16);
-                *reinterpret_cast<uint4 *>(d + pa) = v;
-            } else {  // head or tail of the row
-#pragma unroll
-                for (int e = 0; e < VE; e++) {
-                    const int64_t x = p0 + e;
-                    if (x >= pa && x < pb) d[x] = o[e];
-                }
-            }
-        }
-    }
-}
-
-template <int MODE, typename T>
-__global__ void __launch_bounds__(kWinBlock) k_resample_window_nodata(const T *__restrict__ src, T *__restrict__ dst,
-                                                                      WinParams P, T nd) {
-    const int64_t band = blockIdx.z;
-    window_group_nodata<MODE, T>(src + band * P.src_band_stride, dst + band * P.dst_band_stride, P, nd, blockIdx.x,
-                                 gridDim.x, blockIdx.y, gridDim.y, threadIdx.x);
-}
-
-template <typename T>
-static void launch_window_nodata(hipStream_t st, dim3 grid, int32_t mode, const void *src, void *dst,
-                                 const WinParams &P, double nodata) {
-    const T *s = static_cast<const T *>(src);
-    T *d = static_cast<T *>(dst);
-    const T nd = nd_cast<T>(nodata);
-    if (mode == FRS_RESAMPLE_NEAREST)
-        k_resample_window_nodata<kWindowNearest, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd);
-    else if (mode == FRS_RESAMPLE_BILINEAR)
-        k_resample_window_nodata<kWindowBilinear, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd);
-    else
-        k_resample_window_nodata<kWindowAverage, T><<<grid, kWinBlock, 0, st>>>(s, d, P, nd);
-}
-
-// window_job with a nodata value (already validated: check_window_nodata below)
-static int window_nodata_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_dev, const frs_raster_desc *d,
-                             void *dst_dev, const frs_window_map *map, int32_t mode, double nodata) {
-    const int es = dtype_size(d->dtype);
-    WinParams P;
-    P.src_h = s->height, P.src_w = s->width, P.dst_h = d->height, P.dst_w = d->width;
-    P.src_row_stride = s->row_stride, P.src_band_stride = s->band_stride;
-    P.dst_row_stride = d->row_stride, P.dst_band_stride = d->band_stride;
-    P.x0 = map->x0, P.y0 = map->y0, P.width = map->width, P.height = map->height, P.fill = map->fill;
-    // window_job's grid
-    const int64_t cpr = (d->width + 16 / es - 1) / (16 / es) + 1;
-    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(cpr / kWinBlock, 65535));
-    const dim3 grid((unsigned)gx, (unsigned)std::min<int64_t>(d->height, kWinMaxGridY), (unsigned)d->nbands);
-    hipStream_t st = ctx->stream;
-    hipEvent_t ev;
-    prof_begin(ctx, "resample", &ev);
-    switch (d->dtype) {
-    case FRS_DT_U8: launch_window_nodata<uint8_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
-    case FRS_DT_U16: launch_window_nodata<uint16_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
-    case FRS_DT_I16: launch_window_nodata<int16_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
-    case FRS_DT_I32: launch_window_nodata<int32_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
-    case FRS_DT_U32: launch_window_nodata<uint32_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
-    case FRS_DT_F32: launch_window_nodata<float>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
-    default: launch_window_nodata<double>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_U8: launch_window<uint8_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_U16: launch_window<uint16_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_I16: launch_window<int16_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_I32: launch_window<int32_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_U32: launch_window<uint32_t>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    case FRS_DT_F32: launch_window<float>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
+    default: launch_window<double>(st, grid, mode, src_dev, dst_dev, P, nodata); break;
     }
     prof_end(ctx, "resample", ev);
     FRS_HIP(hipGetLastError());
@@ -433,69 +330,47 @@ static int check_window_pointers(frs_ctx *ctx, const frs_raster_desc *src, const
     return FRS_OK;
 }
 
+// frs_resample_window*: every check, then the job between the device rasters `sp` / `dp`, or (host) between staged
+// copies of the host rasters they point at.  nodata: null without one.
+static int window_entry(frs_ctx *ctx, const frs_raster_desc *src, const void *sp, const frs_raster_desc *dst, void *dp,
+                        const frs_window_map *map, int32_t mode, const double *nodata, bool host) {
+    if (!ctx) return FRS_E_ARG;
+    if (int rc = check_unsynced(ctx)) return rc;
+    if (int rc = nodata ? check_window_nodata_args(ctx, src, dst, map, mode, *nodata)
+                        : check_window_args(ctx, src, dst, map, mode))
+        return rc;
+    if (int rc = check_window_pointers(ctx, src, sp, dst, dp)) return rc;
+    FRS_HIP(hipSetDevice(ctx->device));
+    if (!host) return window_job(ctx, src, sp, dst, dp, map, mode, nodata);
+    return run_staged(ctx, sp, window_bytes(src), dp, window_bytes(dst), [&](const void *src_dev, void *dst_dev) {
+        return window_job(ctx, src, src_dev, dst, dst_dev, map, mode, nodata);
+    });
+}
+
 }  // namespace frs
 
 extern "C" {
 
 int frs_resample_window_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
                                const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map, int32_t mode) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = frs::check_window_args(ctx, src, dst, map, mode)) return rc;
-    if (int rc = frs::check_window_pointers(ctx, src, src_dev, dst, dst_dev)) return rc;
-    FRS_HIP(hipSetDevice(ctx->device));
-    return frs::window_job(ctx, src, src_dev, dst, dst_dev, map, mode);
+    return frs::window_entry(ctx, src, src_dev, dst, dst_dev, map, mode, nullptr, false);
 }
 
 int frs_resample_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
                         void *dst_host, const frs_window_map *map, int32_t mode) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = frs::check_window_args(ctx, src, dst, map, mode)) return rc;
-    if (int rc = frs::check_window_pointers(ctx, src, src_host, dst, dst_host)) return rc;
-    const size_t sbytes = frs::window_bytes(src), dbytes = frs::window_bytes(dst);
-    FRS_HIP(hipSetDevice(ctx->device));
-    FRS_HIP(ctx->raster_stage.ensure(sbytes));
-    FRS_HIP(ctx->arena_stage.ensure(dbytes));
-    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
-    // the destination goes up first: its row and band padding comes back as it was
-    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = frs::window_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, map, mode)) return rc;
-    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
-    FRS_HIP(hipStreamSynchronize(ctx->stream));
-    return FRS_OK;
+    return frs::window_entry(ctx, src, src_host, dst, dst_host, map, mode, nullptr, true);
 }
 
 int frs_resample_window_nodata_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
                                       const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map,
                                       int32_t mode, double nodata) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = frs::check_window_nodata_args(ctx, src, dst, map, mode, nodata)) return rc;
-    if (int rc = frs::check_window_pointers(ctx, src, src_dev, dst, dst_dev)) return rc;
-    FRS_HIP(hipSetDevice(ctx->device));
-    return frs::window_nodata_job(ctx, src, src_dev, dst, dst_dev, map, mode, nodata);
+    return frs::window_entry(ctx, src, src_dev, dst, dst_dev, map, mode, &nodata, false);
 }
 
 int frs_resample_window_nodata(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host,
                                const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
                                double nodata) {
-    if (!ctx) return FRS_E_ARG;
-    if (int rc = frs::check_unsynced(ctx)) return rc;
-    if (int rc = frs::check_window_nodata_args(ctx, src, dst, map, mode, nodata)) return rc;
-    if (int rc = frs::check_window_pointers(ctx, src, src_host, dst, dst_host)) return rc;
-    const size_t sbytes = frs::window_bytes(src), dbytes = frs::window_bytes(dst);
-    FRS_HIP(hipSetDevice(ctx->device));
-    FRS_HIP(ctx->raster_stage.ensure(sbytes));
-    FRS_HIP(ctx->arena_stage.ensure(dbytes));
-    FRS_HIP(hipMemcpyAsync(ctx->raster_stage.ptr, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
-    // the destination goes up first: its row and band padding comes back as it was
-    FRS_HIP(hipMemcpyAsync(ctx->arena_stage.ptr, dst_host, dbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = frs::window_nodata_job(ctx, src, ctx->raster_stage.ptr, dst, ctx->arena_stage.ptr, map, mode, nodata))
-        return rc;
-    FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
-    FRS_HIP(hipStreamSynchronize(ctx->stream));
-    return FRS_OK;
+    return frs::window_entry(ctx, src, src_host, dst, dst_host, map, mode, &nodata, true);
 }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
-// nodata_groups_host.hip -- run downsample_group_nodata (frs_pyramid.hip) and window_group_nodata (frs_window.hip) on the
-// HOST, lane by lane, against a direct per-pixel evaluation with the scalar functions of frs_nodata.h.  Source and
-// destination live in allocations of exactly their extent, so that a build with the address and undefined-behaviour
-// sanitizers reports any read or write outside them; every destination element outside [height][width] must keep its
-// sentinel.  No GPU is used.  The cases are those of tests/test_gpu_pyramid_nodata.py and test_gpu_window_nodata.py:
-// their shapes, layouts, masks, nodata values, rectangles and destination sizes.
+// nodata_groups_host.hip -- run downsample_group (frs_pyramid.hip) and window_group (frs_window.hip) on the HOST, lane
+// by lane, under both mask policies, against a direct per-pixel evaluation with the scalar functions of frs_nodata.h
+// (Nodata<T>) and of frs_resample.h / frs_window_map.h (NoNodata).  Source and destination live in allocations of
+// exactly their extent, so that a build with the address and undefined-behaviour sanitizers reports any read or write
+// outside them; every destination element outside [height][width] must keep its sentinel.  No GPU is used.  The cases
+// are those of tests/test_gpu_pyramid_nodata.py and test_gpu_window_nodata.py: their shapes, layouts, masks, nodata
+// values, rectangles and destination sizes; the unmasked policy walks the same shapes, layouts, rectangles and sizes
+// over sources of random values, in every instantiation the library launches.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined
 //         -Xarch_host -fno-sanitize-recover=all -I flac_raster_amd/csrc -I include -o nodata_groups_host
@@ -85,6 +87,12 @@ template <typename T> struct Raster {
 
 // mask k of the tests: 0 none, 1 all, 2 checkerboard, 3 ~30 % random, 4 one valid per block, 5 last column and row,
 // 6 a collar of 3 pixels
+template <typename T> static void fill_plain(Raster<T> &s) {
+    for (int64_t c = 0; c < s.C; c++)
+        for (int64_t r = 0; r < s.h; r++)
+            for (int64_t x = 0; x < s.w; x++) s.at(c, r, x) = random_value<T>();
+}
+
 template <typename T> static void fill_source(Raster<T> &s, T nd, int mask) {
     for (int64_t c = 0; c < s.C; c++)
         for (int64_t r = 0; r < s.h; r++)
@@ -119,92 +127,154 @@ template <typename T, typename F> static void check(Raster<T> &d, F want, const 
     }
 }
 
-template <int ES, int DT> static void pyramid_cases() {
+// every lane of a gx x gy grid over the C bands
+template <int ES, int MODE, int DT, typename Mask>
+static void run_pyramid(Raster<typename PyrElem<ES, DT>::T> &s, Raster<typename PyrElem<ES, DT>::T> &d,
+                        const PyrParams &P, const Mask &mask) {
+    const int64_t gx = 1 + (int64_t)(g_rng() % 2), gy = 1 + (int64_t)(g_rng() % 3);
+    for (int64_t c = 0; c < s.C; c++)
+        for (int64_t bx = 0; bx < gx; bx++)
+            for (int64_t by = 0; by < gy; by++)
+                for (uint32_t tid = 0; tid < (uint32_t)kPyrBlock; tid++)
+                    downsample_group<ES, MODE, DT>(s.origin() + c * s.bs, d.origin() + c * d.bs, P, mask, bx, gx, by,
+                                                   gy, tid);
+}
+
+// MASKED: the average under Nodata<T>, every nodata value and mask; otherwise (ES, MODE, DT) under NoNodata
+template <int ES, int MODE, int DT, bool MASKED> static long pyramid_cases() {
     using T = typename PyrElem<ES, DT>::T;
+    const long before = g_cases;
     const int64_t shapes[][2] = {{1, 1}, {2, 2}, {3, 5}, {5, 3}, {33, 67}, {64, 130}, {4, 131}, {3, 9000 / ES}};
-    std::vector<double> nds = {0.0, 5.0};
-    if constexpr (NdFloat<T>::value) {
-        nds.insert(nds.end(), {(double)std::numeric_limits<T>::lowest(), (double)std::numeric_limits<T>::max(), NAN,
-                               -INFINITY});
-    } else {
-        nds.insert(nds.end(), {(double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max()});
+    std::vector<double> nds = {0.0};
+    if constexpr (MASKED) {
+        nds.push_back(5.0);
+        if constexpr (NdFloat<T>::value) {
+            nds.insert(nds.end(), {(double)std::numeric_limits<T>::lowest(), (double)std::numeric_limits<T>::max(), NAN,
+                                   -INFINITY});
+        } else {
+            nds.insert(nds.end(), {(double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max()});
+        }
     }
     for (double ndd : nds)
         for (auto &sh : shapes)
             for (int64_t C : {1, 3})
                 for (int layout = 0; layout < 2; layout++)
-                    for (int mask = 0; mask < 6; mask++) {
-                        const T nd = nd_cast<T>(ndd);
+                    for (int mask = 0; mask < (MASKED ? 6 : 1); mask++) {
                         const int64_t H = sh[0], W = sh[1], h = (H + 1) / 2, w = (W + 1) / 2;
                         const int64_t pad = layout ? 3 : 0, slack = layout ? 5 : 0, lead = layout ? 1 : 0;
                         Raster<T> s(C, H, W, pad, slack, lead), d(C, h, w, pad, slack, lead);
-                        fill_source(s, nd, mask);
                         PyrParams P;
                         P.src_h = H, P.src_w = W, P.dst_h = h, P.dst_w = w;
                         P.src_row_stride = s.rs, P.src_band_stride = s.bs, P.dst_row_stride = d.rs, P.dst_band_stride = d.bs;
-                        const int64_t gx = 1 + (int64_t)(g_rng() % 2), gy = 1 + (int64_t)(g_rng() % 3);
-                        for (int64_t c = 0; c < C; c++)
-                            for (int64_t bx = 0; bx < gx; bx++)
-                                for (int64_t by = 0; by < gy; by++)
-                                    for (uint32_t tid = 0; tid < (uint32_t)kPyrBlock; tid++)
-                                        downsample_group_nodata<ES, DT>(s.origin() + c * s.bs, d.origin() + c * d.bs, P,
-                                                                        nd, bx, gx, by, gy, tid);
-                        snprintf(g_note, sizeof g_note, "ES %d dtype %d nodata %g, %lld x %lld x %lld, layout %d, mask %d",
-                                 ES, DT, ndd, (long long)C, (long long)H, (long long)W, layout, mask);
-                        check(d, [&](int64_t c, int64_t r, int64_t x) {
-                            const bool right = 2 * x + 1 < W, below = 2 * r + 1 < H;
-                            T v[4];
-                            int m = 0;
-                            for (int k = 0; k < 4; k++) {
-                                if ((k & 1 && !right) || (k & 2 && !below)) continue;
-                                const T p = s.at(c, 2 * r + (k >> 1), 2 * x + (k & 1));
-                                if (!nd_is(p, nd)) v[m++] = p;
-                            }
-                            return nd_mean(v, m, nd);
-                        }, "pyramid");
+                        snprintf(g_note, sizeof g_note, "ES %d mode %d dtype %d masked %d nodata %g, %lld x %lld x %lld, layout %d, mask %d",
+                                 ES, MODE, DT, (int)MASKED, ndd, (long long)C, (long long)H, (long long)W, layout, mask);
+                        if constexpr (MASKED) {
+                            const T nd = nd_cast<T>(ndd);
+                            fill_source(s, nd, mask);
+                            run_pyramid<ES, MODE, DT>(s, d, P, Nodata<T>{nd});
+                            check(d, [&](int64_t c, int64_t r, int64_t x) {
+                                const bool right = 2 * x + 1 < W, below = 2 * r + 1 < H;
+                                T v[4];
+                                int m = 0;
+                                for (int k = 0; k < 4; k++) {
+                                    if ((k & 1 && !right) || (k & 2 && !below)) continue;
+                                    const T p = s.at(c, 2 * r + (k >> 1), 2 * x + (k & 1));
+                                    if (!nd_is(p, nd)) v[m++] = p;
+                                }
+                                return nd_mean(v, m, nd);
+                            }, "pyramid, masked");
+                        } else {
+                            fill_plain(s);
+                            run_pyramid<ES, MODE, DT>(s, d, P, NoNodata{});
+                            check(d, [&](int64_t c, int64_t r, int64_t x) {
+                                const bool right = 2 * x + 1 < W, below = 2 * r + 1 < H;
+                                const T a = s.at(c, 2 * r, 2 * x);
+                                if constexpr (MODE == kResampleNearest) return a;
+                                else {
+                                    if (right && below)
+                                        return resample_avg4(a, s.at(c, 2 * r, 2 * x + 1), s.at(c, 2 * r + 1, 2 * x),
+                                                             s.at(c, 2 * r + 1, 2 * x + 1));
+                                    if (right) return resample_avg2(a, s.at(c, 2 * r, 2 * x + 1));
+                                    if (below) return resample_avg2(a, s.at(c, 2 * r + 1, 2 * x));
+                                    return a;
+                                }
+                            }, "pyramid, unmasked");
+                        }
                     }
+    return g_cases - before;
 }
 
-template <int MODE, typename T> static T window_direct(Raster<T> &s, int64_t c, const WinParams &P, T nd, int64_t r, int64_t x) {
+// one output by the definition; nd is read under Nodata<T> only
+template <int MODE, typename T, bool MASKED>
+static T window_direct(Raster<T> &s, int64_t c, const WinParams &P, T nd, int64_t r, int64_t x) {
     const WinAxis ax = win_axis(P.x0, P.width, P.dst_w, P.src_w), ay = win_axis(P.y0, P.height, P.dst_h, P.src_h);
     const T fill = win_result<T>(P.fill);
     if constexpr (MODE == kWindowNearest) {
         const WinNearest nx = win_nearest(ax, x), ny = win_nearest(ay, r);
         if (!(nx.valid && ny.valid)) return fill;
         const T v = s.at(c, ny.i, nx.i);
-        return nd_is(v, nd) ? fill : v;
+        return MASKED && nd_is(v, nd) ? fill : v;
     } else if constexpr (MODE == kWindowBilinear) {
         const WinLinear lx = win_linear(ax, x), ly = win_linear(ay, r);
         if (!(lx.valid && ly.valid)) return fill;
         const T a = s.at(c, ly.i0, lx.i0), b = s.at(c, ly.i0, lx.i1), cc = s.at(c, ly.i1, lx.i0), d = s.at(c, ly.i1, lx.i1);
-        return nd_win_result<T>(nd_bilinear((double)a, (double)b, (double)cc, (double)d, !nd_is(a, nd), !nd_is(b, nd),
-                                            !nd_is(cc, nd), !nd_is(d, nd), lx.t, ly.t), fill, nd);
+        if constexpr (!MASKED)
+            return win_result<T>(win_bilinear_value((double)a, (double)b, (double)cc, (double)d, lx.t, ly.t));
+        else
+            return nd_win_result<T>(nd_bilinear((double)a, (double)b, (double)cc, (double)d, !nd_is(a, nd), !nd_is(b, nd),
+                                                !nd_is(cc, nd), !nd_is(d, nd), lx.t, ly.t), fill, nd);
     } else {
         const WinArea rx = win_area(ax, x), ry = win_area(ay, r);
         if (!(rx.valid && ry.valid)) return fill;
-        NdArea acc;
-        for (int64_t j = ry.i0; j < ry.i1; j++) {
-            for (int64_t i = rx.i0; i < rx.i1; i++) {
-                const T v = s.at(c, j, i);
-                acc.tap(win_area_weight(rx, i), (double)v, !nd_is(v, nd));
+        if constexpr (!MASKED) {
+            double sum = 0.0;
+            for (int64_t j = ry.i0; j < ry.i1; j++) {
+                double row = 0.0;
+                for (int64_t i = rx.i0; i < rx.i1; i++) row = row + win_area_weight(rx, i) * (double)s.at(c, j, i);
+                sum = sum + win_area_weight(ry, j) * row;
             }
-            acc.end_row(win_area_weight(ry, j));
+            return win_result<T>(win_area_value(sum, rx, ry));
+        } else {
+            NdArea acc;
+            for (int64_t j = ry.i0; j < ry.i1; j++) {
+                for (int64_t i = rx.i0; i < rx.i1; i++) {
+                    const T v = s.at(c, j, i);
+                    acc.tap(win_area_weight(rx, i), (double)v, !nd_is(v, nd));
+                }
+                acc.end_row(win_area_weight(ry, j));
+            }
+            return nd_win_result<T>(acc.value(rx, ry), fill, nd);
         }
-        return nd_win_result<T>(acc.value(rx, ry), fill, nd);
     }
 }
 
-template <int MODE, typename T> static void window_cases() {
+template <int MODE, typename T, typename Mask>
+static void run_window(Raster<T> &s, Raster<T> &d, const WinParams &P, const Mask &mask) {
+    const int64_t gx = 1 + (int64_t)(g_rng() % 2), gy = 1 + (int64_t)(g_rng() % 3);
+    for (int64_t c = 0; c < d.C; c++)
+        for (int64_t bx = 0; bx < gx; bx++)
+            for (int64_t by = 0; by < gy; by++)
+                for (uint32_t tid = 0; tid < (uint32_t)kWinBlock; tid++)
+                    window_group<MODE, T>(s.origin() + c * s.bs, d.origin() + c * d.bs, P, mask, bx, gx, by, gy, tid);
+}
+
+template <int MODE, typename T, bool MASKED> static long window_cases() {
+    const long before = g_cases;
     const int64_t H = 37, W = 53;
     const int64_t widths[] = {1, 7, 8, 9, 33, 130, 300}, heights[] = {1, 3, 5, 17, 40};
     std::vector<double> nds = {0.0};
-    if constexpr (NdFloat<T>::value) nds.insert(nds.end(), {NAN, -INFINITY, (double)std::numeric_limits<T>::max()});
-    else nds.insert(nds.end(), {(double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max()});
+    std::vector<int> masks = {0};
+    if constexpr (MASKED) {
+        if constexpr (NdFloat<T>::value) nds.insert(nds.end(), {NAN, -INFINITY, (double)std::numeric_limits<T>::max()});
+        else nds.insert(nds.end(), {(double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max()});
+        masks = {0, 1, 3, 6};
+    }
     for (double ndd : nds)
-        for (int mask : {0, 1, 3, 6}) {
+        for (int mask : masks) {
             const T nd = nd_cast<T>(ndd);
             Raster<T> s(3, H, W, 3, 5, 1);
-            fill_source(s, nd, mask);
+            if constexpr (MASKED) fill_source(s, nd, mask);
+            else fill_plain(s);
             for (int64_t w : widths)
                 for (int64_t h : heights) {
                     const double rects[][4] = {{0.0, 0.0, (double)W, (double)H}, {1.0, 2.0, 2.0 * w, 2.0 * h},
@@ -220,45 +290,61 @@ template <int MODE, typename T> static void window_cases() {
                             P.src_h = H, P.src_w = W, P.dst_h = h, P.dst_w = w;
                             P.src_row_stride = s.rs, P.src_band_stride = s.bs, P.dst_row_stride = d.rs, P.dst_band_stride = d.bs;
                             P.x0 = rc[0], P.y0 = rc[1], P.width = rc[2], P.height = rc[3];
-                            P.fill = NdFloat<T>::value && g_rng() % 3 == 0 ? NAN : g_rng() % 2 ? 200.5 : ndd == ndd && fabs(ndd) < 1e30 ? ndd : 7.0;
-                            const int64_t gx = 1 + (int64_t)(g_rng() % 2), gy = 1 + (int64_t)(g_rng() % 3);
-                            for (int64_t c = 0; c < C; c++)
-                                for (int64_t bx = 0; bx < gx; bx++)
-                                    for (int64_t by = 0; by < gy; by++)
-                                        for (uint32_t tid = 0; tid < (uint32_t)kWinBlock; tid++)
-                                            window_group_nodata<MODE, T>(s.origin() + c * s.bs, d.origin() + c * d.bs, P, nd,
-                                                                         bx, gx, by, gy, tid);
-                            snprintf(g_note, sizeof g_note, "mode %d, %zu-byte elements, nodata %g, mask %d, %lld x %lld, fill %g",
-                                     MODE, sizeof(T), ndd, mask, (long long)h, (long long)w, P.fill);
-                            check(d, [&](int64_t c, int64_t r, int64_t x) { return window_direct<MODE, T>(s, c, P, nd, r, x); },
-                                  "window");
+                            // (a NaN fill is for float rasters with a nodata value only)
+                            P.fill = MASKED && NdFloat<T>::value && g_rng() % 3 == 0 ? NAN : g_rng() % 2 ? 200.5 : ndd == ndd && fabs(ndd) < 1e30 ? ndd : 7.0;
+                            snprintf(g_note, sizeof g_note, "mode %d, %zu-byte elements, masked %d, nodata %g, mask %d, %lld x %lld, fill %g",
+                                     MODE, sizeof(T), (int)MASKED, ndd, mask, (long long)h, (long long)w, P.fill);
+                            if constexpr (MASKED) run_window<MODE, T>(s, d, P, Nodata<T>{nd});
+                            else run_window<MODE, T>(s, d, P, NoNodata{});
+                            check(d, [&](int64_t c, int64_t r, int64_t x) { return window_direct<MODE, T, MASKED>(s, c, P, nd, r, x); },
+                                  MASKED ? "window, masked" : "window, unmasked");
                         }
                 }
         }
+    return g_cases - before;
 }
 
-template <typename T> static void window_modes() {
-    window_cases<kWindowNearest, T>();
-    window_cases<kWindowBilinear, T>();
-    window_cases<kWindowAverage, T>();
+static long g_masked = 0, g_plain = 0;
+static bool g_all_plain = true;  // every unmasked instantiation ran at least one case
+
+static void count(const char *what, int mode, const char *type, long masked, long plain, bool has_masked) {
+    printf("%-8s mode %d %-8s masked %6ld%s unmasked %6ld\n", what, mode, type, masked, has_masked ? " " : "*", plain);
+    g_masked += masked, g_plain += plain;
+    if (plain == 0) g_all_plain = false;
+}
+
+template <int ES, int DT> static void pyramid_dtype(const char *type) {
+    count("pyramid", kResampleAverage, type, pyramid_cases<ES, kResampleAverage, DT, true>(),
+          pyramid_cases<ES, kResampleAverage, DT, false>(), true);
+}
+
+template <typename T> static void window_dtype(const char *type) {
+    count("window", kWindowNearest, type, window_cases<kWindowNearest, T, true>(), window_cases<kWindowNearest, T, false>(), true);
+    count("window", kWindowBilinear, type, window_cases<kWindowBilinear, T, true>(), window_cases<kWindowBilinear, T, false>(), true);
+    count("window", kWindowAverage, type, window_cases<kWindowAverage, T, true>(), window_cases<kWindowAverage, T, false>(), true);
 }
 
 int main() {
-    pyramid_cases<1, FRS_DT_U8>();
-    pyramid_cases<2, FRS_DT_U16>();
-    pyramid_cases<2, FRS_DT_I16>();
-    pyramid_cases<4, FRS_DT_I32>();
-    pyramid_cases<4, FRS_DT_U32>();
-    pyramid_cases<4, FRS_DT_F32>();
-    pyramid_cases<8, FRS_DT_F64>();
-    const long pyr = g_cases;
-    window_modes<uint8_t>();
-    window_modes<uint16_t>();
-    window_modes<int16_t>();
-    window_modes<int32_t>();
-    window_modes<uint32_t>();
-    window_modes<float>();
-    window_modes<double>();
-    printf("pyramid cases %ld, window cases %ld, differing %ld\n", pyr, g_cases - pyr, g_bad);
-    return g_bad ? 1 : 0;
+    // nearest is instantiated per element size and has no masked form (*)
+    count("pyramid", kResampleNearest, "1-byte", 0, pyramid_cases<1, kResampleNearest, 0, false>(), false);
+    count("pyramid", kResampleNearest, "2-byte", 0, pyramid_cases<2, kResampleNearest, 0, false>(), false);
+    count("pyramid", kResampleNearest, "4-byte", 0, pyramid_cases<4, kResampleNearest, 0, false>(), false);
+    count("pyramid", kResampleNearest, "8-byte", 0, pyramid_cases<8, kResampleNearest, 0, false>(), false);
+    pyramid_dtype<1, FRS_DT_U8>("uint8");
+    pyramid_dtype<2, FRS_DT_U16>("uint16");
+    pyramid_dtype<2, FRS_DT_I16>("int16");
+    pyramid_dtype<4, FRS_DT_I32>("int32");
+    pyramid_dtype<4, FRS_DT_U32>("uint32");
+    pyramid_dtype<4, FRS_DT_F32>("float32");
+    pyramid_dtype<8, FRS_DT_F64>("float64");
+    window_dtype<uint8_t>("uint8");
+    window_dtype<uint16_t>("uint16");
+    window_dtype<int16_t>("int16");
+    window_dtype<int32_t>("int32");
+    window_dtype<uint32_t>("uint32");
+    window_dtype<float>("float32");
+    window_dtype<double>("float64");
+    printf("masked cases %ld, unmasked cases %ld, differing %ld\n", g_masked, g_plain, g_bad);
+    if (!g_all_plain) fprintf(stderr, "an unmasked instantiation ran no case\n");
+    return g_bad || !g_all_plain ? 1 : 0;
 }
