@@ -365,7 +365,10 @@ __device__ inline int sel_masks_co(const uint8_t *blob, int64_t nbytes, const in
                     const uint4 cur = *reinterpret_cast<const uint4 *>(base + q0);
                     const uint4 nxt = q0 + 16 < qend ? *reinterpret_cast<const uint4 *>(base + q0 + 16)
                                                      : make_uint4(0, 0, 0, 0);
-                    const bool regs_ok = k + 1 < kSelSteps || lane < 63;  // the window holds the next 16 bytes
+                    // (here nxt is read from memory, so the window holds the next 16 bytes for every lane; the wave's
+                    // last lane keeps the global parse of the CRC form above, whose shuffled window does not hold
+                    // them -- tests/test_gpu_sync_geometry.py decodes headers in those 16 bytes through both forms)
+                    const bool regs_ok = k + 1 < kSelSteps || lane < 63;
                     mask = sel_check_candidates(cur, nxt, raw, q0 - lead, nbytes, blob, soff, ns, channels,
                                                 stream_bps, regs_ok);
                 }
@@ -525,7 +528,7 @@ __device__ inline int sel_count_queue(const uint8_t *blob, int64_t nbytes, const
             const int64_t q0 = qw + 1024 * k + 16 * ln;
             const uint4 cur = *reinterpret_cast<const uint4 *>(base + q0);
             const uint4 nxt = q0 + 16 < qend ? *reinterpret_cast<const uint4 *>(base + q0 + 16) : make_uint4(0, 0, 0, 0);
-            const bool regs_ok = k + 1 < kSelSteps || ln < 63;  // as sel_masks_co: the window holds the next 16 bytes
+            const bool regs_ok = k + 1 < kSelSteps || ln < 63;  // as sel_masks_co's second phase (nxt is from memory)
             const uint32_t mask = sel_check_body(cur, nxt, e & 0xFFFFu, q0 - lead, nbytes, blob, soff, ns, channels,
                                                  stream_bps, regs_ok);
             q[i] = (e & 0xFFFF0000u) | mask;
