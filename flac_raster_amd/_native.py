@@ -43,6 +43,7 @@ EXPORTS = (
     "frs_resample_window_device", "frs_resample_window",
     "frs_downsample2_nodata_device", "frs_downsample2_nodata",
     "frs_resample_window_nodata_device", "frs_resample_window_nodata",
+    "frs_band_stats_device", "frs_band_stats", "frs_band_histogram_device", "frs_band_histogram",
 )
 
 # enum frs_resample
@@ -64,6 +65,33 @@ def compare_groups(count: int, nbands: int, itemsize: int) -> int:
     """Work-groups per band of a compare of `count` elements per band (compare_groups in csrc/frs_compare.hip)."""
     chunk = COMPARE_BLOCK * COMPARE_UNROLL * (16 // itemsize)
     return max(1, min(-(-count // chunk), max(1, COMPARE_MAX_GROUPS // nbands)))
+
+
+# launch constants of k_band_stats / k_band_histogram (csrc/frs_stats.hip: kStBlock, kStUnroll, kStMaxGroups, kHistBlock,
+# kHistUnroll, kHistMaxGroups, kHistMaxBins, kHistCopyBins): a work-group step covers BLOCK * UNROLL 16-byte windows, a
+# band gets one work-group per step up to MAX_GROUPS // nbands, grid-striding beyond that
+STATS_BLOCK = 256
+STATS_UNROLL = 4
+STATS_MAX_GROUPS = 2048
+HIST_BLOCK = 512
+HIST_UNROLL = 4
+HIST_MAX_GROUPS = 1024
+HIST_MAX_BINS = 16384
+HIST_COPY_BINS = 512
+
+
+def stats_items(height: int, width: int, itemsize: int, dense: bool = True) -> int:
+    """16-byte windows (work items) of one band (stats_items in csrc/frs_stats.h): a run of n elements can touch
+    (n + 2 * ve - 2) // ve windows, ve = 16 // itemsize; a dense band is one run, any other one run per row."""
+    ve = 16 // itemsize
+    return (height * width + 2 * ve - 2) // ve if dense else height * ((width + 2 * ve - 2) // ve)
+
+
+def stats_groups(items: int, nbands: int, block: int = STATS_BLOCK, unroll: int = STATS_UNROLL,
+                 max_groups: int = STATS_MAX_GROUPS) -> int:
+    """Work-groups per band of a statistics pass over `items` windows per band (stats_groups in csrc/frs_stats.hip)."""
+    chunk = block * unroll
+    return max(1, min(-(-items // chunk), max(1, max_groups // nbands)))
 
 
 class NativeUnavailable(RuntimeError):
@@ -136,6 +164,34 @@ class WindowMap(ctypes.Structure):
         ("x0", ctypes.c_double), ("y0", ctypes.c_double), ("width", ctypes.c_double), ("height", ctypes.c_double),
         ("fill", ctypes.c_double),
     ]
+
+
+class BandStatsOut(ctypes.Structure):
+    """frs_band_stats_out"""
+    _fields_ = [
+        ("n_valid", ctypes.c_int64), ("n_nodata", ctypes.c_int64), ("n_nan", ctypes.c_int64),
+        ("min", ctypes.c_double), ("max", ctypes.c_double), ("sum", ctypes.c_double),
+        ("isum_hi", ctypes.c_int64), ("isum_lo", ctypes.c_uint64),
+        ("isq_hi", ctypes.c_uint64), ("isq_lo", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        """The fields, with the two 128-bit values joined into Python integers (isum, isq)."""
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["isum"] = (d.pop("isum_hi") << 64) + d.pop("isum_lo")
+        d["isq"] = (d.pop("isq_hi") << 64) + d.pop("isq_lo")
+        return d
+
+
+class HistParams(ctypes.Structure):
+    """frs_hist_params"""
+    _fields_ = [("lo", ctypes.c_double), ("hi", ctypes.c_double), ("nbins", ctypes.c_int32),
+                ("centre", ctypes.c_double)]
+
+
+class BandHistOut(ctypes.Structure):
+    """frs_band_hist_out"""
+    _fields_ = [("below", ctypes.c_uint64), ("above", ctypes.c_uint64), ("m2", ctypes.c_double)]
 
 
 def tile_window_array(windows) -> ctypes.Array:
@@ -264,6 +320,13 @@ def load_library(path: Optional[os.PathLike] = None):
                          (L.frs_resample_window_nodata_device, rw_args), (L.frs_resample_window_nodata, rw_args)):
             fn.restype = i32
             fn.argtypes = args + [ctypes.c_double]
+        st_args = [ctxp, rdp, vp, dp, ctypes.POINTER(BandStatsOut)]
+        hi_args = [ctxp, rdp, vp, dp, ctypes.POINTER(HistParams), ctypes.POINTER(ctypes.c_uint64),
+                   ctypes.POINTER(BandHistOut)]
+        for fn, args in ((L.frs_band_stats_device, st_args), (L.frs_band_stats, st_args),
+                         (L.frs_band_histogram_device, hi_args), (L.frs_band_histogram, hi_args)):
+            fn.restype = i32
+            fn.argtypes = args
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -809,6 +872,56 @@ class Context:
         else:
             self._check(self.lib.frs_resample_window_nodata(*args, float(nodata)))
         return out
+
+    # ---- band statistics and histogram
+    @staticmethod
+    def _nodata_arg(nodata):
+        return None if nodata is None else ctypes.byref(ctypes.c_double(float(nodata)))
+
+    def _stats_host_layout(self, a):
+        a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.dtype not in DTYPE_CODES or a.size == 0:
+            raise ValueError("band statistics need a non-empty (bands, h, w) or (h, w) array of a raster dtype")
+        a, rs, bs = _window_layout(a)
+        nb = a.shape[0] if a.ndim == 3 else 1
+        return a, self.make_raster_desc(a.shape[-2], a.shape[-1], a.dtype, nbands=nb, row_stride=rs, band_stride=bs)
+
+    def band_stats_device(self, ptr: int, desc: RasterDesc, nodata=None, as_dicts: bool = True):
+        """frs_band_stats_device on the device raster at `ptr`, laid out as `desc`: one frs_band_stats_out per band, as
+        dicts (BandStatsOut.as_dict) or the structures.  `nodata` (a number) masks the pixels that hold it."""
+        out = (BandStatsOut * max(int(desc.nbands), 1))()
+        self._check(self.lib.frs_band_stats_device(self.handle, ctypes.byref(desc), ctypes.c_void_p(ptr),
+                                                   self._nodata_arg(nodata), out))
+        return [x.as_dict() for x in out] if as_dicts else list(out)
+
+    def band_stats(self, a: np.ndarray, nodata=None, as_dicts: bool = True):
+        """frs_band_stats on a host raster ((bands, h, w) or (h, w)).  A strided window view of a larger raster is
+        passed by its origin pointer and strides; anything else that is not C-contiguous is copied first."""
+        a, d = self._stats_host_layout(a)
+        out = (BandStatsOut * d.nbands)()
+        self._check(self.lib.frs_band_stats(self.handle, ctypes.byref(d), _p(a), self._nodata_arg(nodata), out))
+        return [x.as_dict() for x in out] if as_dicts else list(out)
+
+    def _hist_call(self, fn, desc, ptr, nodata, lo, hi, nbins, centre):
+        nb, n = max(int(desc.nbands), 1), int(nbins)
+        counts = np.zeros((nb, max(n, 1)), dtype=np.uint64)
+        out = (BandHistOut * nb)()
+        hp = HistParams(float(lo), float(hi), n, float(centre))
+        self._check(fn(self.handle, ctypes.byref(desc), ptr, self._nodata_arg(nodata), ctypes.byref(hp),
+                       counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out))
+        return counts, [{"below": int(o.below), "above": int(o.above), "m2": float(o.m2)} for o in out]
+
+    def band_histogram_device(self, ptr: int, desc: RasterDesc, lo: float, hi: float, nbins: int, nodata=None,
+                              centre: float = 0.0):
+        """frs_band_histogram_device: (counts uint64 [nbands][nbins], [{below, above, m2} per band]) of the device
+        raster at `ptr` under the bin rule of csrc/frs_stats.h; m2 is the float dtypes' sum of (x - centre)^2."""
+        return self._hist_call(self.lib.frs_band_histogram_device, desc, ctypes.c_void_p(ptr), nodata, lo, hi, nbins,
+                               centre)
+
+    def band_histogram(self, a: np.ndarray, lo: float, hi: float, nbins: int, nodata=None, centre: float = 0.0):
+        """frs_band_histogram on a host raster ((bands, h, w) or (h, w)); see band_histogram_device and band_stats."""
+        a, d = self._stats_host_layout(a)
+        return self._hist_call(self.lib.frs_band_histogram, d, _p(a), nodata, lo, hi, nbins, centre)
 
     # ---- bench helpers
     def synth_raster(self, buf: DeviceBuffer, bands: int, height: int, width: int, row0: int = 0,

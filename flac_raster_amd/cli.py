@@ -105,9 +105,15 @@ def create_streaming(
                                                                 "or 'source' (the GeoTIFF's own nodata tag): written "
                                                                 "to the index and the tiles, and kept out of the "
                                                                 "overview averages (single GPU only)"),
+    stats: bool = typer.Option(False, "--stats", help="Extension: compute the band's statistics and a histogram of at "
+                                                      "most 256 bins on the GPU and store them in the index (single "
+                                                      "GPU only)"),
 ):
     """Create Netflix-style streaming FLAC with self-contained tiles"""
     from . import streaming
+    if stats and (gpus > 1 or distributed):
+        typer.echo("Error: --stats runs on one GPU: it cannot be combined with --gpus > 1 or --distributed", err=True)
+        raise typer.Exit(1)
     nd = None
     if nodata is not None:
         if gpus > 1 or distributed:
@@ -157,7 +163,8 @@ def create_streaming(
             index = create_streaming_distributed(input_file, output_file, tile_size)
         else:
             index = streaming.create_streaming(input_file, output_file, tile_size, overviews=overviews,
-                                               resampling=resampling, max_levels=overview_levels, nodata=nd)
+                                               resampling=resampling, max_levels=overview_levels, nodata=nd,
+                                               stats=stats)
         top = max(streaming.overview_levels(index))
         if overviews:
             typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles, {top} overview levels)")
@@ -165,6 +172,10 @@ def create_streaming(
             typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles)")
         if "nodata" in index:
             typer.echo(f"NODATA: {index['nodata']}")
+        if "statistics" in index:
+            st = index["statistics"]
+            typer.echo(f"STATS: valid={st['valid']} nodata={st['nodata_count']} nan={st['nan']} min={st['min']} "
+                       f"max={st['max']} mean={st['mean']} std={st['std']}")
         if verify:
             from . import geotiff
             ex = streaming.verify_streaming(output_file, geotiff.read(input_file).data[0])
@@ -382,6 +393,11 @@ def info(file_path: str = typer.Argument(..., help="FLAC or TIFF file to inspect
                 con.print(f"  Overview levels: {len(levels) - 1}")
                 con.print(f"  CRS: {index.get('crs')}")
                 con.print(f"  Nodata: {index['nodata'] if 'nodata' in index else 'None'}")
+                if "statistics" in index:
+                    from .stats import format_band
+                    con.print("  Statistics (level 0):")
+                    for line in format_band(1, streaming.index_statistics(index))[1:]:
+                        con.print("  " + line, highlight=False)
                 con.print(f"  File size: {len(buf) / 1024 / 1024:.2f} MB")
                 return
             except Exception:
@@ -445,6 +461,75 @@ def info(file_path: str = typer.Argument(..., help="FLAC or TIFF file to inspect
     else:
         con.print(f"[red]Error: Unsupported file format: {suffix}[/red]")
         raise typer.Exit(1)
+
+
+@app.command()
+def stats(
+    file_path: Path = typer.Argument(..., help="TIFF or streaming FLAC file"),
+    level: Optional[int] = typer.Option(None, "--level", min=0, help="Overview level K of a streaming file written "
+                                                                     "with --overviews (0: full resolution)"),
+    nodata: Optional[str] = typer.Option(None, "--nodata", help="Override the file's nodata value with a number, or "
+                                                                "'none' to count every pixel (default: the file's "
+                                                                "own value)"),
+    bins: int = typer.Option(256, "--bins", help="Histogram bins at most (1..16384); an integer band whose value range "
+                                                 "fits gets one bin per value"),
+    percentiles: str = typer.Option("2,50,98", "--percentiles", help="Percentiles to read off the histogram"),
+    as_json: bool = typer.Option(False, "--json", help="Print one JSON document"),
+):
+    """Band statistics and histogram, computed on the GPU (extension)"""
+    from .stats import MAX_BINS
+    # every argument rule is checked before anything is read
+    if not 1 <= bins <= MAX_BINS:
+        typer.echo(f"Error: --bins must be 1..{MAX_BINS}, got {bins}", err=True)
+        raise typer.Exit(1)
+    try:
+        from fractions import Fraction
+        qs = [p.strip() for p in percentiles.split(",") if p.strip()]
+        if not qs or not all(0 <= Fraction(q) <= 100 for q in qs):
+            raise ValueError(percentiles)
+    except (ValueError, ZeroDivisionError):
+        typer.echo(f"Error: --percentiles must be numbers 0..100 separated by commas, got {percentiles!r}", err=True)
+        raise typer.Exit(1)
+    nd = "file" if nodata is None else _nodata_option(nodata, "none")
+    if not file_path.exists():
+        typer.echo(f"Error: Input file does not exist: {file_path}", err=True)
+        raise typer.Exit(1)
+    suffix = file_path.suffix.lower()
+    if suffix not in (".tif", ".tiff", ".flac"):
+        typer.echo(f"Error: Unsupported file format: {suffix}", err=True)
+        raise typer.Exit(1)
+    if level is not None and suffix != ".flac":
+        typer.echo("Error: --level applies to streaming FLAC files: a TIFF has one level", err=True)
+        raise typer.Exit(1)
+    try:
+        from .stats import format_band, raster_file_statistics, with_percentiles
+        res = raster_file_statistics(file_path, level=level or 0, nodata=nd, bins=bins)
+        res["bands"] = [with_percentiles(b, qs) for b in res["bands"]]
+        if as_json:
+            from .stats import statistics_to_index
+            doc = dict(res, nodata=None if res["nodata"] is None else _nodata_word(res["nodata"]),
+                       bands=[dict(statistics_to_index(b), percentiles=b["percentiles"]) for b in res["bands"]])
+            typer.echo(json.dumps(doc))
+        else:
+            at = f", level {res['level']}" if suffix == ".flac" else ""
+            typer.echo(f"{file_path}: {res['width']} x {res['height']}, {len(res['bands'])} band(s), {res['dtype']}"
+                       f"{at}, nodata {res['nodata']}")
+            for i, b in enumerate(res["bands"], 1):
+                for line in format_band(i, b, qs):
+                    typer.echo(line)
+    except (KeyError, LookupError, ValueError) as e:
+        typer.echo(f"Error: {e}", err=True)
+        raise typer.Exit(1)
+    except Exception as e:
+        log.exception("Statistics failed")
+        typer.echo(f"Error during statistics: {e}", err=True)
+        raise typer.Exit(1)
+
+
+def _nodata_word(v):
+    """A nodata value as JSON holds it (streaming._nodata_to_index)"""
+    from .streaming import _nodata_to_index
+    return _nodata_to_index(v)
 
 
 @app.command()

@@ -117,6 +117,10 @@ struct frs_ctx {
     // decoders' interleaved output that frs_decode_tiles_window* places from
     DevBuf place_tab, place_stage;
     HostPin place_pin;
+    // band statistics and histogram (frs_band_stats*, frs_band_histogram*): per-work-group partial records, the
+    // histogram's per-work-group counter slabs and per-band counts, the pinned host copy of the results
+    DevBuf st_part, st_slab, st_counts;
+    HostPin st_pin;
     // page-locked host allocations of this context (frs_host_malloc): a C5 decode whose output lies in one returns
     // when the kernel's last work-group has published it, before the stream's completion signal (`unsynced` then
     // makes the next call check the stream for an asynchronous fault first)
@@ -197,5 +201,16 @@ int run_staged(frs_ctx *ctx, const void *src_host, size_t sbytes, void *dst_host
     FRS_HIP(hipMemcpyAsync(dst_host, ctx->arena_stage.ptr, dbytes, hipMemcpyDeviceToHost, ctx->stream));
     FRS_HIP(hipStreamSynchronize(ctx->stream));
     return FRS_OK;
+}
+// The host-pointer form of a job that reads one raster and returns its results to the host itself (frs_band_stats,
+// frs_band_histogram): the raster goes up to the context's staging buffer, job(src_dev) runs on it and synchronises.
+// The copy keeps the host raster's position within a 16-byte window, so that a job whose summation order depends on
+// the alignment gives the host raster's bits for it.
+template <typename Job> int run_staged(frs_ctx *ctx, const void *src_host, size_t sbytes, Job job) {
+    const size_t phase = reinterpret_cast<uintptr_t>(src_host) & 15u;
+    FRS_HIP(ctx->raster_stage.ensure(sbytes + 16));
+    void *dev = ctx->raster_stage.at<char>(phase);
+    FRS_HIP(hipMemcpyAsync(dev, src_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
+    return job(dev);
 }
 }  // namespace frs

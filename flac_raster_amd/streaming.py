@@ -28,6 +28,11 @@ the overview levels are built with the masked step (frs_downsample2_nodata_devic
 ``overviews``) and ``read_window`` resamples with the masked kernel, so that a nodata collar or hole is never averaged
 into its neighbours.  Level 0's frames are what they are without nodata.  A file without the key reads exactly as
 before.
+
+Statistics (extension, ``create_streaming*(stats=True)``): the index gains a top-level ``"statistics"`` key with the
+level-0 band's valid / nodata / NaN counts, min, max, mean, std and a histogram of at most 256 bins
+(``stats.band_statistics``; non-finite numbers as the same JSON strings), masked by the nodata value in force.  The
+frames and every other key are what they are without it; ``index_statistics`` reads the key back.
 """
 from __future__ import annotations
 
@@ -122,6 +127,13 @@ def index_nodata(index: Dict) -> Optional[float]:
     """The nodata value a streaming index carries (its "nodata" key), or None."""
     v = index.get("nodata")
     return None if v is None else float(v)
+
+
+def index_statistics(index: Dict) -> Optional[Dict]:
+    """The statistics of the level-0 band a streaming index carries (its "statistics" key, written by
+    create_streaming*(stats=True)), as stats.band_statistics returns a band's, or None."""
+    from .stats import statistics_from_index
+    return statistics_from_index(index.get("statistics"))
 
 
 def overview_levels(index: Dict) -> List[int]:
@@ -356,11 +368,11 @@ def encode_band_tiles_device(ctx: Context, raster_ptr: int, height: int, width: 
 
 def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs: Optional[str], output: Path,
                                 tile_size: int, ctx: Optional[Context], tm: Dict[str, float], resampling: str,
-                                max_levels: Optional[int], nodata=None) -> Dict:
+                                max_levels: Optional[int], nodata=None, stats: bool = False) -> Dict:
     """create_streaming_array(overviews=True): the band goes up once; level k is made from level k - 1 on the device
     (frs_downsample2_device) and encoded there like a raster of its own.  Device memory held at any time: the band,
     two level buffers and one arena (sized for level 0, the largest).  With `nodata` (already in the dtype's terms) the
-    step is the masked one."""
+    step is the masked one.  With `stats` the uploaded band's statistics go into the index."""
     if resampling not in RESAMPLING:
         raise ValueError(f"resampling must be one of {RESAMPLING}, got {resampling!r}")
     ctx = ctx or default_context()
@@ -374,8 +386,11 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
     bufs = [ctx.alloc(band.nbytes)]
     pyr_s = 0.0
     encs: List[EncodedTiles] = []
+    band_stats = None
     try:
         bufs[0].upload(band)
+        if stats:
+            band_stats = _band_statistics_device(ctx, bufs[0].ptr, H, W, dtype, nodata)
         arena = ctx.alloc(ctx.arena_bound(d0))
         bufs.append(arena)
         # level k lives in lv[k % 2] (level 1 and 2 get a buffer each, level k + 2 fits in level k's)
@@ -421,6 +436,8 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
     index["overviews"] = {"resampling": resampling, "levels": levels}
     if nodata is not None:
         index["overviews"]["nodata_aware"] = True
+    if band_stats is not None:
+        index["statistics"] = band_stats
     head = streaming_head(index)
     t2 = time.perf_counter()
     fd = os.open(output, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
@@ -438,31 +455,74 @@ def _create_streaming_overviews(band: np.ndarray, transform: geotiff.Affine, crs
     return index
 
 
+STATS_INDEX_BINS = 256  # bins of the histogram create_streaming*(stats=True) stores at most
+
+
+def _band_statistics_device(ctx: Context, ptr: int, height: int, width: int, dtype, nodata) -> Dict:
+    """The index's "statistics" value of the dense band at device pointer `ptr`."""
+    from .stats import _device_statistics, statistics_to_index
+    d = ctx.make_raster_desc(height, width, dtype)
+    return statistics_to_index(_device_statistics(ctx, ptr, d, nodata, STATS_INDEX_BINS)[0])
+
+
+def _encode_band_tiles_with_statistics(band: np.ndarray, tile_size: int, ctx: Context, nodata):
+    """create_streaming_array(stats=True) without overviews: the band goes up once, is encoded there
+    (encode_band_tiles_device: the frames encode_band_tiles gives) and its statistics are taken from the same
+    buffer.  Returns (EncodedTiles, the index's "statistics" value)."""
+    H, W = band.shape
+    if H == 0 or W == 0:
+        raise ValueError("statistics of an empty band")
+    _, bps = audio_params(1, min(tile_size, H), band.dtype)
+    d = ctx.make_desc(H, W, band.dtype, nbands=1, tile_h=tile_size, tile_w=tile_size, sample_rate=44100,
+                      bits_per_sample=bps)
+    bufs = [ctx.alloc(band.nbytes)]
+    try:
+        bufs[0].upload(band)
+        bufs.append(ctx.alloc(ctx.arena_bound(d)))
+        enc = encode_band_tiles_device(ctx, bufs[0].ptr, H, W, band.dtype, tile_size, bufs[1],
+                                       pinned=band.nbytes >= (64 << 20))
+        return enc, _band_statistics_device(ctx, bufs[0].ptr, H, W, band.dtype, nodata)
+    finally:
+        for b in bufs:
+            b.close()
+
+
 def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Optional[str], output: Path,
                            tile_size: int = 1024, ctx: Optional[Context] = None,
                            timings: Optional[Dict[str, float]] = None, overviews: bool = False,
-                           resampling: str = "average", max_levels: Optional[int] = None, nodata=None) -> Dict:
+                           resampling: str = "average", max_levels: Optional[int] = None, nodata=None,
+                           stats: bool = False) -> Dict:
     """cli.py:620-804 on an in-memory band-1 array: one GPU encode of every tile, headers and index on the host,
     tiles written from the arena with parallel pwritev.  Returns the index; `timings` gets the stage seconds.
     overviews=True (extension) appends reduced-resolution levels (module docstring): `resampling` is "average" or
     "nearest", `max_levels` caps their number; `timings` then also gets pyramid_s (inside encode_s).  `nodata`
-    (extension, a number the band's dtype holds: nodata_for_dtype) marks pixels without data (module docstring)."""
+    (extension, a number the band's dtype holds: nodata_for_dtype) marks pixels without data (module docstring).
+    stats=True (extension) puts the band's statistics (stats.band_statistics: counts, min, max, mean, std and a
+    histogram of at most 256 bins, masked by the nodata value in force) into the index under "statistics"; the band
+    then goes up once for the encode and the statistics together.  Without it the file and the path taken are what
+    they are without the option."""
     tm = timings if timings is not None else {}
     if nodata is not None:
         nodata = nodata_for_dtype(nodata, band.dtype)
     if overviews:
         return _create_streaming_overviews(band, transform, crs, output, tile_size, ctx, tm, resampling, max_levels,
-                                           nodata)
+                                           nodata, stats)
     t0 = time.perf_counter()
     H, W = band.shape
-    # large jobs: frames back into page-locked memory (DMA rate, no page faults) and written from there
-    enc = encode_band_tiles(band, tile_size, ctx, pinned=band.nbytes >= (64 << 20))
+    band_stats = None
+    if stats:
+        enc, band_stats = _encode_band_tiles_with_statistics(band, tile_size, ctx or default_context(), nodata)
+    else:
+        # large jobs: frames back into page-locked memory (DMA rate, no page faults) and written from there
+        enc = encode_band_tiles(band, tile_size, ctx, pinned=band.nbytes >= (64 << 20))
     t1 = time.perf_counter()
     headers, frames, body = streaming_headers(enc, transform, crs, W, H, tile_size, band.dtype, nodata=nodata)
     index = {"crs": str(crs), "transform": list(transform), "width": W, "height": H, "tile_size": tile_size,
              "frames": frames}
     if nodata is not None:
         index["nodata"] = _nodata_to_index(nodata)
+    if band_stats is not None:
+        index["statistics"] = band_stats
     head = streaming_head(index)
     t2 = time.perf_counter()
     fd = os.open(output, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
@@ -481,13 +541,13 @@ def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Opt
 def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
                      ctx: Optional[Context] = None, timings: Optional[Dict[str, float]] = None,
                      materialize: bool = False, overviews: bool = False, resampling: str = "average",
-                     max_levels: Optional[int] = None, nodata=None) -> Dict:
+                     max_levels: Optional[int] = None, nodata=None, stats: bool = False) -> Dict:
     """cli.py:620-804 without the console output: writes the streaming file, returns the index.  Band 1 only
     (cli.py:698-699): an uncompressed band-sequential (or single-band) file is encoded straight from its memory map
     (no host copy of the band); otherwise its strips / tiles are decoded.  `timings` gets read_s + the stages of
     create_streaming_array.  materialize=True reads the band into host memory first (read_s is then the whole read;
     otherwise the band's pages are read while the encode copies them, inside encode_s).  overviews / resampling /
-    max_levels / nodata: as create_streaming_array; nodata="source" takes the GeoTIFF's GDAL_NODATA tag (ValueError
+    max_levels / nodata / stats: as create_streaming_array; nodata="source" takes the GeoTIFF's GDAL_NODATA tag (ValueError
     when the file has none)."""
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
@@ -506,7 +566,7 @@ def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
         tm["read_s"] = time.perf_counter() - t0
         transform = transform or geotiff.Affine(1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
         index = create_streaming_array(band, transform, crs, output_file, tile_size, ctx, tm, overviews=overviews,
-                                       resampling=resampling, max_levels=max_levels, nodata=nodata)
+                                       resampling=resampling, max_levels=max_levels, nodata=nodata, stats=stats)
         del band
     tm["total_s"] = time.perf_counter() - t0
     return index

@@ -346,6 +346,57 @@ int frs_resample_window_nodata(frs_ctx *ctx, const frs_raster_desc *src, const v
                                const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
                                double nodata);
 
+/* Statistics and histogram of the bands of ONE raster, each in one pass over every band: what a caller needs to stretch
+ * a window for display, check a nodata collar or sanity-check a conversion (gdalinfo -stats -hist).  The reference has
+ * no such call.  The raster is band-planar [nbands][height][width] elements with row / band strides in elements
+ * (frs_raster_desc, all seven dtypes, nbands 1..8).  nodata is null, or points at the nodata value (predicate of the
+ * nodata-aware calls above).  csrc/frs_stats.h holds the arithmetic for host and device; the definitions are this
+ * library's own.
+ * Validity: a pixel is nodata by that predicate (only when a value is given); otherwise NaN (float dtypes only);
+ * otherwise valid.  +-inf are valid values.  Everything but the three counts is over the valid pixels.
+ * frs_band_stats*, out_host[nbands]:
+ *   n_valid, n_nodata, n_nan   the three classes (they add up to height*width)
+ *   min, max                   as double, exact for every dtype; NaN when n_valid == 0
+ *   sum                        integers: the exact sum rounded once; floats: an fp64 sum of (double)v in a fixed order
+ *                              that depends on shape, dtype and layout only (bit-reproducible)
+ *   isum_hi, isum_lo           integer dtypes: the exact sum as a signed 128-bit value; 0 for floats
+ *   isq_hi, isq_lo             integer dtypes: the exact sum of squares as an unsigned 128-bit value; 0 for floats
+ * frs_band_histogram*, with scale = (double)nbins / (hi - lo) computed once and x = (double)v of a valid pixel:
+ * x < lo counts in `below`, x > hi in `above`, otherwise bin floor((x - lo) * scale), clamped to nbins - 1.  With
+ * lo = m, hi = M + 1, nbins = M - m + 1 every integer value m .. M has a bin of its own.  counts_host is
+ * [nbands][nbins]; out_host[nbands] holds below, above and, for float dtypes, m2 = the sum of (x - centre)^2 over the
+ * valid pixels in the same kind of fixed order (0 for integer dtypes, whose exact sum of squares the first call gives).
+ * Nothing outside [height][width] is read (16-byte loads cut at the 16-byte boundaries of each row, or of the band when
+ * row_stride == width).  FRS_E_ARG, before anything is launched or written: the descriptor errors of
+ * frs_resample_window*, a null pointer or one not aligned to the element size, a nodata value the dtype cannot hold,
+ * nbins outside 1..16384, lo, hi, hi - lo or centre not finite, hi <= lo, and a shape in which one work-group would fold
+ * more than 2^30 elements (beyond ~2^40 elements).  Synchronous on the context stream; profile entries "band_stats" and
+ * "band_hist".  The host variants copy the raster through the context's staging buffer. */
+typedef struct {
+    int64_t n_valid, n_nodata, n_nan;
+    double min, max, sum;
+    int64_t isum_hi;
+    uint64_t isum_lo;
+    uint64_t isq_hi, isq_lo;
+} frs_band_stats_out;
+typedef struct {
+    double lo, hi;
+    int32_t nbins;
+    double centre;
+} frs_hist_params;
+typedef struct {
+    uint64_t below, above;
+    double m2;
+} frs_band_hist_out;
+int frs_band_stats_device(frs_ctx *ctx, const frs_raster_desc *desc, const void *raster_dev, const double *nodata,
+                          frs_band_stats_out *out_host);
+int frs_band_stats(frs_ctx *ctx, const frs_raster_desc *desc, const void *raster_host, const double *nodata,
+                   frs_band_stats_out *out_host);
+int frs_band_histogram_device(frs_ctx *ctx, const frs_raster_desc *desc, const void *raster_dev, const double *nodata,
+                              const frs_hist_params *params, uint64_t *counts_host, frs_band_hist_out *out_host);
+int frs_band_histogram(frs_ctx *ctx, const frs_raster_desc *desc, const void *raster_host, const double *nodata,
+                       const frs_hist_params *params, uint64_t *counts_host, frs_band_hist_out *out_host);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
@@ -385,7 +436,7 @@ int frs_synth_raster_device(frs_ctx *ctx, int16_t *dev, int32_t bands, int64_t h
 void *frs_ctx_stream(frs_ctx *ctx);
 /* Average device time (ms) of the named kernel over the launches since the last reset, measured with
  * HIP events on the context stream (kernel: "encode" = the frame-encode kernel, "analyze", "stats",
- * "compact", "decode", "compare", "place", "pyramid", "resample"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
+ * "compact", "decode", "compare", "place", "pyramid", "resample", "band_stats", "band_hist"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
 int frs_profile_enable(frs_ctx *ctx, int on);
 double frs_profile_avg_ms(frs_ctx *ctx, const char *kernel);
 void frs_profile_reset(frs_ctx *ctx);
