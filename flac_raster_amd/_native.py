@@ -44,6 +44,7 @@ EXPORTS = (
     "frs_downsample2_nodata_device", "frs_downsample2_nodata",
     "frs_resample_window_nodata_device", "frs_resample_window_nodata",
     "frs_band_stats_device", "frs_band_stats", "frs_band_histogram_device", "frs_band_histogram",
+    "frs_render_window_device", "frs_render_window",
 )
 
 # enum frs_resample
@@ -194,6 +195,28 @@ class BandHistOut(ctypes.Structure):
     _fields_ = [("below", ctypes.c_uint64), ("above", ctypes.c_uint64), ("m2", ctypes.c_double)]
 
 
+class RenderParams(ctypes.Structure):
+    """frs_render_params"""
+    _fields_ = [("lo", ctypes.c_double), ("hi", ctypes.c_double), ("lut", ctypes.c_void_p), ("n", ctypes.c_int32),
+                ("nodata_rgba", ctypes.c_uint32), ("channels", ctypes.c_int32)]
+
+
+RENDER_MAX_LUT = 4096  # csrc/frs_render.h: kRenderMaxLut
+
+
+def pack_rgba(rgba) -> int:
+    """nodata_rgba as frs_render_params takes it: R | G << 8 | B << 16 | A << 24, from that integer or from (r, g, b, a)."""
+    if isinstance(rgba, (int, np.integer)):
+        v = int(rgba)
+        if not 0 <= v <= 0xFFFFFFFF:
+            raise ValueError("a packed rgba value must fit 32 bits")
+        return v
+    r, g, b, a = (int(x) for x in rgba)
+    if any(not 0 <= x <= 255 for x in (r, g, b, a)):
+        raise ValueError("rgba components must be 0..255")
+    return r | g << 8 | b << 16 | a << 24
+
+
 def tile_window_array(windows) -> ctypes.Array:
     """(TileWindow * n) from TileWindow structures or (col_off, row_off, width, height) rows."""
     if isinstance(windows, ctypes.Array) and windows._type_ is TileWindow:
@@ -327,6 +350,10 @@ def load_library(path: Optional[os.PathLike] = None):
                          (L.frs_band_histogram_device, hi_args), (L.frs_band_histogram, hi_args)):
             fn.restype = i32
             fn.argtypes = args
+        rn_args = rw_args + [dp, ctypes.POINTER(RenderParams)]
+        for fn in (L.frs_render_window_device, L.frs_render_window):
+            fn.restype = i32
+            fn.argtypes = rn_args
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -871,6 +898,54 @@ class Context:
             self._check(self.lib.frs_resample_window(*args))
         else:
             self._check(self.lib.frs_resample_window_nodata(*args, float(nodata)))
+        return out
+
+    # ---- render
+    @staticmethod
+    def _render_params(lo, hi, lut, nodata_rgba, channels):
+        """(RenderParams, the array its LUT pointer refers to).  `lut` is uint8 (n, 4); its length is the C-ABI's to
+        judge, so that a caller sees the library's message."""
+        t = np.ascontiguousarray(lut, dtype=np.uint8)
+        if t.ndim != 2 or t.shape[1] != 4:
+            raise ValueError("the LUT must be a uint8 array of shape (n, 4)")
+        return RenderParams(float(lo), float(hi), t.ctypes.data if t.size else None, int(t.shape[0]),
+                            pack_rgba(nodata_rgba), int(channels)), t
+
+    def render_window_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, out_h: int, out_w: int, rect,
+                             mode, lo: float, hi: float, lut, nodata_rgba=0, channels: int = 4, nodata=None,
+                             dst_row_stride: Optional[int] = None) -> None:
+        """frs_render_window_device: the rectangle rect = (x0, y0, width, height) of the one-band device raster at
+        src_ptr (laid out as src_desc), resampled by `mode` onto out_h x out_w pixels and written as interleaved uint8
+        [out_h][out_w][channels] at dst_ptr, rows dst_row_stride bytes apart (out_w * channels by default).  A value v
+        becomes lut[index] with the bin rule of csrc/frs_render.h over [lo, hi]; `lut` is uint8 (n, 4) R, G, B, A,
+        n <= 4096.  A pixel without data (outside the source, masked by `nodata`, or NaN) takes nodata_rgba, a packed
+        integer (pack_rgba) or (r, g, b, a).  channels: 1 = R, 2 = R, A, 4 = R, G, B, A."""
+        rp, keep = self._render_params(lo, hi, lut, nodata_rgba, channels)
+        rs = int(out_w) * int(channels) if dst_row_stride is None else int(dst_row_stride)
+        dd = self.make_raster_desc(out_h, out_w, np.uint8, row_stride=rs)
+        m = self._window_map(rect, 0.0)
+        self._check(self.lib.frs_render_window_device(
+            self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr), ctypes.byref(dd), ctypes.c_void_p(dst_ptr),
+            ctypes.byref(m), self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(rp)))
+        del keep
+
+    def render_window(self, a: np.ndarray, rect, out_shape, mode, lo: float, hi: float, lut, nodata_rgba=0,
+                      channels: int = 4, nodata=None) -> np.ndarray:
+        """frs_render_window on a host raster (H, W): uint8 (h, w, channels) of out_shape = (h, w); see
+        render_window_device."""
+        a = np.ascontiguousarray(a)
+        if a.ndim != 2 or a.dtype not in DTYPE_CODES or a.size == 0:
+            raise ValueError("render_window needs a non-empty (H, W) array of a raster dtype")
+        h, w = (int(v) for v in out_shape)
+        rp, keep = self._render_params(lo, hi, lut, nodata_rgba, channels)
+        sd = self.make_raster_desc(a.shape[0], a.shape[1], a.dtype)
+        dd = self.make_raster_desc(h, w, np.uint8, row_stride=w * int(channels))
+        out = np.zeros((max(h, 0), max(w, 0), max(int(channels), 0)), dtype=np.uint8)
+        m = self._window_map(rect, 0.0)
+        self._check(self.lib.frs_render_window(
+            self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), ctypes.byref(m),
+            self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(rp)))
+        del keep
         return out
 
     # ---- band statistics and histogram

@@ -526,6 +526,113 @@ def stats(
         raise typer.Exit(1)
 
 
+@app.command()
+def render(
+    flac_url: str = typer.Argument(..., help="Streaming FLAC file (local path or HTTP URL)"),
+    bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="Bounding box as 'xmin,ymin,xmax,ymax' (default: "
+                                                                   "the raster's bounds)"),
+    out_size: Optional[str] = typer.Option(None, "--out-size", help="The image as exactly WxH pixels"),
+    max_size: Optional[int] = typer.Option(None, "--max-size", help="The image's longer side as N pixels, the other "
+                                                                    "by the box's aspect ratio"),
+    output: Path = typer.Option(..., "--output", "-o", help="Output .png, or .tif (georeferenced, 8-bit)"),
+    stretch: str = typer.Option("percentile:2,98", "--stretch", help="minmax, percentile:p,q, stddev:k or range:lo,hi"),
+    stats_from: str = typer.Option("auto", "--stats-from", help="auto, file (the index's statistics: one stretch for "
+                                                                "the whole raster) or window (the decoded window's)"),
+    colormap: str = typer.Option("gray", "--colormap", help="gray, gray_r, heat, terrain, diverging, or a text file "
+                                                            "of 't r g b [a]' lines"),
+    gamma: float = typer.Option(1.0, "--gamma", help="Gamma of the ramp (> 0)"),
+    transfer: str = typer.Option("linear", "--transfer", help="linear or log"),
+    resampling: str = typer.Option("average", "--resampling", help="nearest, bilinear or average"),
+    level: Optional[int] = typer.Option(None, "--level", min=0, help="Read overview level K instead of the one that "
+                                                                     "fits"),
+    nodata: Optional[str] = typer.Option(None, "--nodata", help="Override the file's nodata value with a number, or "
+                                                                "'none' to render without one"),
+    channels: int = typer.Option(4, "--channels", help="1 (grey), 2 (grey, alpha) or 4 (R, G, B, A)"),
+    force: bool = typer.Option(False, "--force", help="Overwrite the output file"),
+):
+    """Render a window of a streaming file as a stretched 8-bit colour image on the GPU (extension)"""
+    from . import render as rn
+    from . import streaming
+    # every argument rule is checked before anything is read
+    def fail(msg: str):
+        typer.echo(f"Error: {msg}", err=True)
+        raise typer.Exit(1)
+
+    if (out_size is None) == (max_size is None):
+        fail("give exactly one of --out-size WxH and --max-size N")
+    size = None
+    if out_size is not None:
+        parts = out_size.lower().split("x")
+        if len(parts) != 2 or not all(p.isascii() and p.isdigit() for p in parts) or min(int(p) for p in parts) < 1:
+            fail(f"--out-size must be WxH with W and H >= 1, got {out_size!r}")
+        size = (int(parts[0]), int(parts[1]))
+    elif max_size < 1:
+        fail(f"--max-size must be >= 1, got {max_size}")
+    suffix = output.suffix.lower()
+    if suffix not in (".png", ".tif", ".tiff"):
+        fail(f"the output must be .png or .tif, got {output.name!r}")
+    if channels not in (1, 2, 4):
+        fail(f"--channels must be 1, 2 or 4, got {channels}")
+    if stats_from not in streaming.STATS_FROM:
+        fail(f"--stats-from must be one of {', '.join(streaming.STATS_FROM)}")
+    if resampling not in streaming.RESAMPLING_READ:
+        fail(f"--resampling must be one of {', '.join(streaming.RESAMPLING_READ)}")
+    if transfer not in rn.TRANSFERS:
+        fail(f"--transfer must be one of {', '.join(rn.TRANSFERS)}")
+    if not (gamma > 0 and gamma != float("inf")):
+        fail(f"--gamma must be a finite number > 0, got {gamma}")
+    try:
+        rn.parse_stretch(stretch)
+    except ValueError as e:
+        fail(str(e))
+    nd = "index" if nodata is None else _nodata_option(nodata, "none")
+    coords = None
+    if bbox is not None:
+        try:
+            coords = _bbox(bbox)
+            if not (coords[2] > coords[0] and coords[3] > coords[1]):
+                raise ValueError("xmax > xmin and ymax > ymin are needed")
+        except (ValueError, IndexError) as e:
+            fail(f"Invalid bbox format. Use 'xmin,ymin,xmax,ymax': {e}")
+    ramp = colormap
+    if colormap not in rn.COLORMAPS:  # a file: the one thing read before the raster, and an argument like the others
+        if not Path(colormap).is_file():
+            fail(f"--colormap must be one of {', '.join(rn.COLORMAPS)} or a file; got {colormap!r}")
+        try:
+            ramp = rn.load_colormap(colormap)
+        except ValueError as e:
+            fail(f"--colormap {colormap}: {e}")
+    if output.exists() and not force:
+        fail(f"{output} exists; use --force to overwrite it")
+    try:
+        from . import geotiff
+        _, index = streaming.read_index(flac_url)
+        if coords is None:
+            coords = list(geotiff.bounds_of(geotiff.Affine(*index["transform"][:6]), int(index["width"]),
+                                            int(index["height"])))
+        if size is None:
+            size = rn.max_size_shape(coords[2] - coords[0], coords[3] - coords[1], max_size)
+        img, tr = streaming.render_window(flac_url, coords, size[0], size[1], stretch=stretch, stats_from=stats_from,
+                                          colormap=ramp, gamma=gamma, transfer=transfer, resampling=resampling,
+                                          level=level, nodata=nd, channels=channels)
+        if suffix == ".png":
+            from .png import write_png
+            write_png(output, img)
+        else:
+            crs = index.get("crs")
+            epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
+            geotiff.write(output, img.transpose(2, 0, 1), transform=geotiff.Affine(*tr[:6]), epsg=epsg,
+                          alpha=channels > 1)
+        typer.echo(f"SUCCESS: rendered {size[0]}x{size[1]}x{channels} ({stretch}, {resampling}) -> {output}")
+    except (KeyError, LookupError, ValueError) as e:
+        typer.echo(f"Error: {e}", err=True)
+        raise typer.Exit(1)
+    except Exception as e:
+        log.exception("Render failed")
+        typer.echo(f"Error during render: {e}", err=True)
+        raise typer.Exit(1)
+
+
 def _nodata_word(v):
     """A nodata value as JSON holds it (streaming._nodata_to_index)"""
     from .streaming import _nodata_to_index

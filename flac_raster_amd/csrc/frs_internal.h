@@ -121,6 +121,7 @@ struct frs_ctx {
     // histogram's per-work-group counter slabs and per-band counts, the pinned host copy of the results
     DevBuf st_part, st_slab, st_counts;
     HostPin st_pin;
+    DevBuf render_lut;  // render (frs_render_window*): the call's colour look-up table
     // page-locked host allocations of this context (frs_host_malloc): a C5 decode whose output lies in one returns
     // when the kernel's last work-group has published it, before the stream's completion signal (`unsynced` then
     // makes the next call check the stream for an asynchronous fault first)
@@ -185,6 +186,12 @@ int place_job(frs_ctx *ctx, const frs_raster_desc *d, const void *tiles_dev, con
 // is null, or points at the nodata value (the masked average of frs_nodata.h; nearest is the same with and without).
 int downsample_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src, const frs_raster_desc *d, void *dst,
                    int32_t mode, const double *nodata);
+// The checks frs_resample_window* and frs_render_window* share (frs_window.hip): a raster descriptor; the mode and the
+// rectangle of a mapping, and its fill unless with_fill is false; elements from a raster's origin to the end of its
+// last row (-1: that does not fit 63 bits with room for the element size).
+int check_window_desc(frs_ctx *ctx, const frs_raster_desc *d);
+int check_window_map(frs_ctx *ctx, const frs_window_map *map, int32_t mode, bool with_fill);
+int64_t window_extent(const frs_raster_desc *d);
 // May `nd` be the nodata value of a raster of dtype `dt` (frs_nodata.h: nd_representable)?
 bool nodata_ok(int dt, double nd);
 

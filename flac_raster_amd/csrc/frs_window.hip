@@ -14,8 +14,8 @@
 //                              and the row's alignment are uniform over the work-group.
 //
 // Both kernels are one lane function, window_group, with a mask policy (frs_nodata.h): NoNodata, or Nodata<T> with the
-// nodata value.  The policy reaches only WinRow::pixel, what one output is computed from its taps; the mapping, the
-// chunks and the stores do not know of it.
+// nodata value.  The policy reaches only WinRow::pixel (frs_window_row.h, shared with frs_render.hip), what one output
+// is computed from its taps; the mapping, the chunks and the stores do not know of it.
 //
 // Store side, as in frs_place.hip and frs_pyramid.hip: a destination row is cut at the 16-byte boundaries of the
 // DESTINATION; a chunk that lies wholly inside the row leaves as one aligned 16-byte store per lane, the first and last
@@ -33,102 +33,12 @@
 #include "frs_internal.h"
 #include "frs_nodata.h"
 #include "frs_window_map.h"
+#include "frs_window_row.h"
 
 namespace frs {
 
 constexpr int kWinBlock = 256;        // threads per work-group
 constexpr int kWinMaxGridY = 32768;   // destination rows beyond this are strided over
-
-struct WinParams {
-    int64_t src_h, src_w, dst_h, dst_w;
-    int64_t src_row_stride, src_band_stride, dst_row_stride, dst_band_stride;
-    double x0, y0, width, height, fill;
-};
-
-// What a destination row needs of the y axis, and one output of that row.  `mask` is NoNodata, or Nodata<T>: then a
-// nodata tap is left out of the output, and an output without a valid tap is `fill`.
-template <int MODE, typename T, typename Mask> struct WinRow;
-
-template <typename T, typename Mask> struct WinRow<kWindowNearest, T, Mask> {
-    const T *s0;
-    bool valid;
-    Mask mask;
-    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, const Mask &mask_)
-        : mask(mask_) {
-        const WinNearest n = win_nearest(ay, r);
-        valid = n.valid, s0 = src + n.i * P.src_row_stride;
-    }
-    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
-        const WinNearest n = win_nearest(ax, x);
-        if constexpr (Mask::masked) {
-            if (!(valid && n.valid)) return fill;
-            const T v = s0[n.i];
-            return nd_is(v, mask.nd) ? fill : v;
-        } else {
-            return valid && n.valid ? s0[n.i] : fill;
-        }
-    }
-};
-
-template <typename T, typename Mask> struct WinRow<kWindowBilinear, T, Mask> {
-    const T *s0, *s1;
-    double t;
-    bool valid;
-    Mask mask;
-    __host__ __device__ WinRow(const T *src, const WinParams &P, const WinAxis &ay, int64_t r, const Mask &mask_)
-        : mask(mask_) {
-        const WinLinear l = win_linear(ay, r);
-        valid = l.valid, t = l.t;
-        s0 = src + l.i0 * P.src_row_stride, s1 = src + l.i1 * P.src_row_stride;
-    }
-    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
-        const WinLinear l = win_linear(ax, x);
-        if (!(valid && l.valid)) return fill;
-        if constexpr (Mask::masked) {
-            const T a = s0[l.i0], b = s0[l.i1], c = s1[l.i0], d = s1[l.i1], nd = mask.nd;
-            return nd_win_result<T>(nd_bilinear((double)a, (double)b, (double)c, (double)d, !nd_is(a, nd),
-                                                !nd_is(b, nd), !nd_is(c, nd), !nd_is(d, nd), l.t, t),
-                                    fill, nd);
-        } else {
-            const double a = (double)s0[l.i0], b = (double)s0[l.i1], c = (double)s1[l.i0], d = (double)s1[l.i1];
-            return win_result<T>(win_bilinear_value(a, b, c, d, l.t, t));
-        }
-    }
-};
-
-template <typename T, typename Mask> struct WinRow<kWindowAverage, T, Mask> {
-    const T *src;
-    int64_t row_stride;
-    WinArea ry;
-    Mask mask;
-    __host__ __device__ WinRow(const T *src_, const WinParams &P, const WinAxis &ay, int64_t r, const Mask &mask_)
-        : src(src_), row_stride(P.src_row_stride), ry(win_area(ay, r)), mask(mask_) {}
-    __host__ __device__ T pixel(const WinAxis &ax, int64_t x, T fill) const {
-        const WinArea rx = win_area(ax, x);
-        if (!(ry.valid && rx.valid)) return fill;
-        if constexpr (Mask::masked) {
-            NdArea acc;
-            for (int64_t j = ry.i0; j < ry.i1; j++) {
-                const T *s = src + j * row_stride;
-                for (int64_t i = rx.i0; i < rx.i1; i++) {
-                    const T v = s[i];
-                    acc.tap(win_area_weight(rx, i), (double)v, !nd_is(v, mask.nd));
-                }
-                acc.end_row(win_area_weight(ry, j));
-            }
-            return nd_win_result<T>(acc.value(rx, ry), fill, mask.nd);
-        } else {
-            double sum = 0.0;
-            for (int64_t j = ry.i0; j < ry.i1; j++) {
-                const T *s = src + j * row_stride;
-                double row = 0.0;
-                for (int64_t i = rx.i0; i < rx.i1; i++) row = row + win_area_weight(rx, i) * (double)s[i];
-                sum = sum + win_area_weight(ry, j) * row;
-            }
-            return win_result<T>(win_area_value(sum, rx, ry));
-        }
-    }
-};
 
 // One lane's share of a work-group: lane tid of work-group (bx of gx, by of gy) of one band (src / dst are the band's
 // origins).  (Plain C++, so that a host program can run it lane by lane against a direct evaluation.)
@@ -242,7 +152,7 @@ static int window_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_de
 
 // elements from a raster's origin to the end of its last row, or -1 when that does not fit 63 bits (with room for the
 // element size)
-static int64_t window_extent(const frs_raster_desc *d) {
+int64_t window_extent(const frs_raster_desc *d) {
     int64_t x, y;
     if (__builtin_mul_overflow((int64_t)d->nbands - 1, d->nbands > 1 ? d->band_stride : 0, &x) ||
         __builtin_mul_overflow(d->height - 1, d->row_stride, &y) || __builtin_add_overflow(x, y, &x) ||
@@ -251,8 +161,9 @@ static int64_t window_extent(const frs_raster_desc *d) {
     return x;
 }
 
-// argument checks of frs_resample_window*, before anything is sized, copied or launched
-static int check_window_desc(frs_ctx *ctx, const frs_raster_desc *d) {
+// argument checks of frs_resample_window*, before anything is sized, copied or launched (the descriptor's and the
+// mapping's are frs_render_window*'s as well: frs_internal.h)
+int check_window_desc(frs_ctx *ctx, const frs_raster_desc *d) {
     if (!d) { ctx->err = "null desc"; return FRS_E_ARG; }
     if (d->height < 1 || d->width < 1) { ctx->err = "resample: height and width must be >= 1"; return FRS_E_ARG; }
     if (d->row_stride < d->width) { ctx->err = "row_stride < width"; return FRS_E_ARG; }
@@ -268,14 +179,8 @@ static int check_window_desc(frs_ctx *ctx, const frs_raster_desc *d) {
 
 static bool window_coord_ok(double v) { return v == v && v > -4503599627370496.0 && v < 4503599627370496.0; }  // 2^52
 
-static int check_window_args(frs_ctx *ctx, const frs_raster_desc *src, const frs_raster_desc *dst,
-                             const frs_window_map *map, int32_t mode) {
-    if (int rc = check_window_desc(ctx, src)) return rc;
-    if (int rc = check_window_desc(ctx, dst)) return rc;
-    if (src->dtype != dst->dtype || src->nbands != dst->nbands) {
-        ctx->err = "resample: source and destination differ in dtype or nbands";
-        return FRS_E_ARG;
-    }
+// mode and rectangle, and the fill unless it is ignored
+int check_window_map(frs_ctx *ctx, const frs_window_map *map, int32_t mode, bool with_fill) {
     if (mode != FRS_RESAMPLE_NEAREST && mode != FRS_RESAMPLE_AVERAGE && mode != FRS_RESAMPLE_BILINEAR) {
         ctx->err = "resample: bad mode";
         return FRS_E_ARG;
@@ -288,12 +193,23 @@ static int check_window_args(frs_ctx *ctx, const frs_raster_desc *src, const frs
         ctx->err = "resample: the rectangle must be finite, with coordinates below 2^52 in magnitude";
         return FRS_E_ARG;
     }
-    if (!(map->fill - map->fill == 0.0)) { ctx->err = "resample: fill must be finite"; return FRS_E_ARG; }
+    if (with_fill && !(map->fill - map->fill == 0.0)) { ctx->err = "resample: fill must be finite"; return FRS_E_ARG; }
     if (!(map->width > 0.0) || !(map->height > 0.0)) {
         ctx->err = "resample: the rectangle's width and height must be > 0";
         return FRS_E_ARG;
     }
     return FRS_OK;
+}
+
+static int check_window_args(frs_ctx *ctx, const frs_raster_desc *src, const frs_raster_desc *dst,
+                             const frs_window_map *map, int32_t mode) {
+    if (int rc = check_window_desc(ctx, src)) return rc;
+    if (int rc = check_window_desc(ctx, dst)) return rc;
+    if (src->dtype != dst->dtype || src->nbands != dst->nbands) {
+        ctx->err = "resample: source and destination differ in dtype or nbands";
+        return FRS_E_ARG;
+    }
+    return check_window_map(ctx, map, mode, true);
 }
 
 // frs_resample_window_nodata*: the same checks, but a float raster may be filled with NaN, and the nodata value must be

@@ -369,16 +369,22 @@ def read(path) -> GeoRaster:
 
 def write(path, data: np.ndarray, transform: Optional[Affine] = None, epsg: Optional[int] = None,
           nodata: Optional[float] = None, compress: Optional[str] = None, predictor: int = 1,
-          tile: Optional[int] = None, planar: int = 1, rows_per_strip: Optional[int] = None) -> None:
+          tile: Optional[int] = None, planar: int = 1, rows_per_strip: Optional[int] = None,
+          alpha: bool = False) -> None:
     """Write (count, height, width) GTiff (GDAL-like layout): ~8 KB strips by default (or `rows_per_strip` rows), or
     `tile` x `tile` tiles; chunky (planar 1) or band-sequential (planar 2) samples; uncompressed or
     ``compress="deflate"`` with optional horizontal differencing (predictor 2).  Uncompressed strips are written
-    straight from the array (no staging copy: a multi-GB raster streams to the file)."""
+    straight from the array (no staging copy: a multi-GB raster streams to the file).  ``alpha=True`` marks the last
+    of at least two bands as unassociated alpha (ExtraSamples = 2); four uint8 bands are then photometric RGB.  Without
+    it the file is what it was before the keyword existed."""
     a = np.asarray(data)
     if a.ndim == 2:
         a = a[None]
     count, H, W = a.shape
     dt = a.dtype
+    if alpha and count < 2:
+        raise ValueError("alpha needs at least two bands: the last one is the alpha")
+    rgb = dt == np.uint8 and (count == 3 or (alpha and count == 4))
     a = np.ascontiguousarray(a.astype(dt.newbyteorder("<"), copy=False))
     chunky = planar == 1 or count == 1
     cs = count if chunky else 1
@@ -430,7 +436,7 @@ def write(path, data: np.ndarray, transform: Optional[Affine] = None, epsg: Opti
     add(257, 3 if H < 65536 else 4, H)
     add(258, 3, [dt.itemsize * 8] * count)
     add(259, 3, 8 if compress == "deflate" else 1)
-    add(262, 3, 2 if (count == 3 and dt == np.uint8) else 1)
+    add(262, 3, 2 if rgb else 1)
     if not tile:
         add(273, 16 if big else 4, [0] * len(sizes))  # patched below
     add(277, 3, count)
@@ -445,7 +451,9 @@ def write(path, data: np.ndarray, transform: Optional[Affine] = None, epsg: Opti
         add(323, 3, int(tile))
         add(324, 16 if big else 4, [0] * len(chunks))  # patched below
         add(325, 16 if big else 4, [len(c) for c in chunks])
-    if count > 1 and not (count == 3 and dt == np.uint8):
+    if alpha:
+        add(338, 3, [0] * (count - (3 if rgb else 1) - 1) + [2])
+    elif count > 1 and not rgb:
         add(338, 3, [0] * (count - 1))
     add(339, 3, [sfmt] * count)
     if transform is not None:

@@ -1071,6 +1071,110 @@ def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, o
     return _download_raster(dst, dtype, out_h, out_w), req["transform"]
 
 
+STATS_FROM = ("auto", "file", "window")
+RENDER_WINDOW_BINS = 256  # bins of the histogram stats_from="window" takes at most
+
+
+def _file_statistics_for(index: Dict, nd: Optional[float]) -> Dict:
+    """The index's "statistics" for a render under the nodata value `nd` in force; LookupError when the index has
+    none, ValueError when they were taken under another nodata value."""
+    st = index_statistics(index)
+    if st is None:
+        raise LookupError('the file has no "statistics" in its index (create-streaming --stats writes them); '
+                          'use stats_from="window" or a range:lo,hi stretch')
+    own = index_nodata(index)
+    same = (nd is None and own is None) or (nd is not None and own is not None
+                                            and (nd == own or (math.isnan(nd) and math.isnan(own))))
+    if not same:
+        raise ValueError(f"the file's statistics were taken with nodata {own}, the render uses {nd}; "
+                         'use stats_from="window"')
+    return st
+
+
+def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, out_h: int,
+                  stretch: str = "percentile:2,98", stats_from: str = "auto", colormap="gray", gamma: float = 1.0,
+                  transfer: str = "linear", lut_size: Optional[int] = None, resampling: str = "average",
+                  level: Optional[int] = None, nodata="index", channels: int = 4, nodata_rgba=(0, 0, 0, 0),
+                  ctx: Optional[Context] = None):
+    """Extension: bbox = [xmin, ymin, xmax, ymax] of band 1 as a stretched 8-bit image of exactly out_w x out_h pixels.
+    It is read_window up to the decoded device window (window_request, fetch_tiles, decode_into_window); then
+    frs_render_window_device (the definition in include/flac_raster_amd.h) resamples the window onto the requested
+    grid, maps every value to a colour and writes interleaved uint8 pixels, and only those out_h * out_w * channels
+    bytes are downloaded.  A pixel without data (outside the raster, masked by the nodata value in force, NaN) takes
+    `nodata_rgba`; a bbox that misses the raster gives an image of nothing else without a GPU call.
+      stretch      render.stretch_limits: "minmax", "percentile:p,q", "stddev:k" or "range:lo,hi" give (lo, hi)
+      stats_from   where the stretch's statistics come from.  "file": the index's "statistics" (create-streaming
+                   --stats): LookupError when the index has none, ValueError when the nodata value in force differs from
+                   the index's.  "window": frs_band_stats_device and frs_band_histogram_device (256 bins at most) on
+                   the decoded device window before it is resampled; nothing but the records is downloaded.  "auto":
+                   "file" when it applies, else "window".  A range:lo,hi stretch needs no statistics and runs neither
+                   pass.  "window" makes neighbouring map tiles stretch differently -- each sees its own values --
+                   which is why "file" is preferred: one stretch for the whole raster.
+      colormap, gamma, transfer, lut_size   render.build_lut; lut_size defaults to 256, or to 4096 when gamma != 1 or
+                   transfer != "linear"
+      channels     1 = R, 2 = R, A, 4 = R, G, B, A
+    `resampling`, `level` and `nodata` are read_window's.  Returns (uint8 array (out_h, out_w, channels), transform
+    list)."""
+    from . import render as rn
+    from ._native import pack_rgba
+    if resampling not in RESAMPLING_READ:
+        raise ValueError(f"resampling must be one of {', '.join(RESAMPLING_READ)}; got {resampling!r}")
+    if stats_from not in STATS_FROM:
+        raise ValueError(f"stats_from must be one of {', '.join(STATS_FROM)}; got {stats_from!r}")
+    channels = int(channels)
+    if channels not in (1, 2, 4):
+        raise ValueError(f"channels must be 1, 2 or 4; got {channels}")
+    kind, _ = rn.parse_stretch(stretch)
+    lut = rn.build_lut(colormap, rn.default_lut_size(gamma, transfer) if lut_size is None else lut_size, gamma,
+                       transfer)
+    packed = pack_rgba(nodata_rgba)
+    src = Source(flac_url)
+    n, index = read_index(src)
+    nd = nodata_in_force(index, nodata)
+    file_stats = None
+    if kind != "range" and stats_from != "window":
+        try:
+            file_stats = _file_statistics_for(index, nd)
+        except (LookupError, ValueError):
+            if stats_from == "file":
+                raise
+    req = window_request(index, bbox, out_w, out_h, level)
+    out_w, out_h = req["out_w"], req["out_h"]
+    if not req["frames"]:
+        out = np.empty((out_h, out_w, channels), dtype=np.uint8)
+        rgba = [packed & 0xFF, (packed >> 8) & 0xFF, (packed >> 16) & 0xFF, packed >> 24]
+        out[...] = {1: rgba[:1], 2: [rgba[0], rgba[3]], 4: rgba}[channels]
+        return out, req["transform"]
+    ctx = ctx or default_context()
+    win = req["window"]
+    datas = fetch_tiles(src, req["frames"], n)
+    wdev, dtype = decode_into_window(datas, req["frames"], (win["col_off"], win["row_off"]),
+                                     (win["height"], win["width"]), ctx)
+    dst = None
+    try:
+        if nd is not None:
+            nd = nodata_for_dtype(nd, dtype)
+        sd = ctx.make_raster_desc(win["height"], win["width"], dtype)
+        if kind == "range":
+            stats = None
+        elif file_stats is not None:
+            stats = file_stats
+        else:
+            from .stats import _device_statistics
+            stats = _device_statistics(ctx, wdev.ptr, sd, nd, RENDER_WINDOW_BINS)[0]
+        lo, hi = rn.stretch_limits(stats, stretch)
+        dst = ctx.alloc(out_h * out_w * channels)
+        ctx.render_window_device(wdev.ptr, sd, dst.ptr, out_h, out_w, req["rect"], resampling, lo, hi, lut,
+                                 nodata_rgba=packed, channels=channels, nodata=nd)
+        out = np.empty((out_h, out_w, channels), dtype=np.uint8)
+        dst.download(out=out)
+    finally:
+        wdev.close()
+        if dst is not None:
+            dst.close()
+    return out, req["transform"]
+
+
 def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0):
     """Every tile of a streaming file (of overview level `level`) in one batched decode, placed into the level's full
     raster in device memory.  Returns (DeviceBuffer, dtype, level_index(index, level))."""

@@ -397,6 +397,47 @@ int frs_band_histogram_device(frs_ctx *ctx, const frs_raster_desc *desc, const v
 int frs_band_histogram(frs_ctx *ctx, const frs_raster_desc *desc, const void *raster_host, const double *nodata,
                        const frs_hist_params *params, uint64_t *counts_host, frs_band_hist_out *out_host);
 
+/* Render a rectangle of ONE band as stretched 8-bit colour: frs_resample_window* fused with a quantiser, a colour
+ * look-up table and an alpha for "no data", so that a windowed read leaves the device as the w x h x C bytes a viewer
+ * shows.  The reference has no such call; csrc/frs_render.h holds the arithmetic for host and device, the definition is
+ * this library's own.  The source is one band (nbands == 1) of any of the seven dtypes, laid out as in
+ * frs_resample_window*; map, mode and nodata (null, or a pointer at the nodata value) mean what they mean there, but
+ * map->fill is ignored.  One output pixel comes from one resampled value v in the source dtype and a flag has_data:
+ *   v, has_data   v is exactly what frs_resample_window* (the _nodata form when nodata is given) writes for the pixel:
+ *                 same taps, weights, rounding and nudge.  has_data is false exactly where that call writes fill (an
+ *                 axis is invalid, masked nearest hit a nodata tap, a masked output has no valid weight) and, for float
+ *                 rasters, where v is NaN.  +-inf are data.
+ *   quantise      scale = (double)n / (hi - lo), computed once.  x = (double)v < lo gives index 0, x > hi gives n - 1,
+ *                 otherwise min((int64)floor((x - lo) * scale), n - 1): frs_band_histogram*'s bin rule, every step one
+ *                 IEEE fp64 operation.
+ *   colour        rgba = lut[index]; lut holds n entries of 4 bytes R, G, B, A (a host pointer: the call copies it).  A
+ *                 pixel without data takes nodata_rgba = R | G << 8 | B << 16 | A << 24.  Gamma, a logarithmic transfer
+ *                 and the colour ramp are all in the LUT, which is why n goes up to 4096.
+ *   channels      C = 1: R;  C = 2: R, A;  C = 4: R, G, B, A.
+ * The destination is pixel-interleaved uint8 [height][width][C]: dst->dtype FRS_DT_U8, dst->width in pixels,
+ * dst->row_stride in BYTES (>= width * C), dst->nbands 1.  No byte outside [height][width * C] of any row is written
+ * (whole 16-byte chunks of a destination row by aligned 16-byte stores, the rest byte by byte); nothing is read outside
+ * the source's [H][W].  FRS_E_ARG, before anything is sized, copied or launched: everything frs_resample_window*
+ * rejects of the descriptors, the mode, the rectangle, the nodata value and the pointers (the source's aligned to its
+ * element size), and nbands != 1, channels not 1, 2 or 4, n outside 1..4096, a null LUT, lo or hi or hi - lo not finite,
+ * hi <= lo, a destination that is not uint8, a byte row stride < width * C, and source and destination byte ranges that
+ * overlap.  Synchronous on the context stream; profile entry "render".  frs_render_window takes host rasters: both are
+ * copied through the context's staging buffers (the destination goes up first and comes back whole, so its padding
+ * survives). */
+typedef struct {
+    double lo, hi;
+    const uint8_t *lut; /* host: n * 4 bytes */
+    int32_t n;
+    uint32_t nodata_rgba;
+    int32_t channels;
+} frs_render_params;
+int frs_render_window_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev, const frs_raster_desc *dst,
+                             void *dst_dev, const frs_window_map *map, int32_t mode, const double *nodata,
+                             const frs_render_params *render);
+int frs_render_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host, const frs_raster_desc *dst,
+                      void *dst_host, const frs_window_map *map, int32_t mode, const double *nodata,
+                      const frs_render_params *render);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
