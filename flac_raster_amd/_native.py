@@ -45,6 +45,7 @@ EXPORTS = (
     "frs_resample_window_nodata_device", "frs_resample_window_nodata",
     "frs_band_stats_device", "frs_band_stats", "frs_band_histogram_device", "frs_band_histogram",
     "frs_render_window_device", "frs_render_window",
+    "frs_render_shaded_window_device", "frs_render_shaded_window",
 )
 
 # enum frs_resample
@@ -204,6 +205,12 @@ class RenderParams(ctypes.Structure):
 RENDER_MAX_LUT = 4096  # csrc/frs_render.h: kRenderMaxLut
 
 
+class ShadeParams(ctypes.Structure):
+    """frs_shade_params"""
+    _fields_ = [("lx", ctypes.c_double), ("ly", ctypes.c_double), ("lz", ctypes.c_double), ("kx", ctypes.c_double),
+                ("ky", ctypes.c_double), ("table", ctypes.c_void_p)]
+
+
 def pack_rgba(rgba) -> int:
     """nodata_rgba as frs_render_params takes it: R | G << 8 | B << 16 | A << 24, from that integer or from (r, g, b, a)."""
     if isinstance(rgba, (int, np.integer)):
@@ -354,6 +361,9 @@ def load_library(path: Optional[os.PathLike] = None):
         for fn in (L.frs_render_window_device, L.frs_render_window):
             fn.restype = i32
             fn.argtypes = rn_args
+        for fn in (L.frs_render_shaded_window_device, L.frs_render_shaded_window):
+            fn.restype = i32
+            fn.argtypes = rn_args + [ctypes.POINTER(ShadeParams)]
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -946,6 +956,67 @@ class Context:
             self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), ctypes.byref(m),
             self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(rp)))
         del keep
+        return out
+
+    # ---- hillshaded render
+    @staticmethod
+    def _shade_params(light, kx, ky, table):
+        """(ShadeParams, the array its table pointer refers to).  `light` is (lx, ly, lz), `table` 256 uint8; what the
+        five doubles may be is the C-ABI's to judge."""
+        t = np.ascontiguousarray(table, dtype=np.uint8)
+        if t.shape != (256,):
+            raise ValueError("the shade table must be 256 uint8 values")
+        lx, ly, lz = (float(v) for v in light)
+        return ShadeParams(lx, ly, lz, float(kx), float(ky), t.ctypes.data), t
+
+    def render_shaded_window_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, out_h: int, out_w: int,
+                                    rect, mode, lo: float, hi: float, lut, light, kx: float, ky: float, table,
+                                    nodata_rgba=0, channels: int = 4, nodata=None,
+                                    dst_row_stride: Optional[int] = None) -> None:
+        """frs_render_shaded_window_device: render_window_device with hillshade (the definition in
+        include/flac_raster_amd.h).  light = (lx, ly, lz) is the unit vector towards the light (render.light_vector),
+        kx = z_factor / (8 cell_x) and ky = z_factor / (8 cell_y) for the ground size of an output pixel, `table` the
+        256 uint8 multipliers of the shade levels (render.shade_table)."""
+        rp, keep = self._render_params(lo, hi, lut, nodata_rgba, channels)
+        sp, keep2 = self._shade_params(light, kx, ky, table)
+        rs = int(out_w) * int(channels) if dst_row_stride is None else int(dst_row_stride)
+        dd = self.make_raster_desc(out_h, out_w, np.uint8, row_stride=rs)
+        m = self._window_map(rect, 0.0)
+        self._check(self.lib.frs_render_shaded_window_device(
+            self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr), ctypes.byref(dd), ctypes.c_void_p(dst_ptr),
+            ctypes.byref(m), self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(rp),
+            ctypes.byref(sp)))
+        del keep, keep2
+
+    def render_shaded_window(self, a: np.ndarray, rect, out, mode, lo: float, hi: float, lut, light, kx: float,
+                             ky: float, table, nodata_rgba=0, channels: int = 4, nodata=None,
+                             dst_row_stride: Optional[int] = None, out_shape=None) -> np.ndarray:
+        """frs_render_shaded_window on a host raster (H, W).  `out` is a shape (h, w) -- then a new uint8 (h, w,
+        channels) is returned -- or a writable uint8 buffer that holds the destination [h][w * channels] at its start
+        with rows dst_row_stride bytes apart (out_shape = (h, w) then): it is returned, padding as it was."""
+        a = np.ascontiguousarray(a)
+        if a.ndim != 2 or a.dtype not in DTYPE_CODES or a.size == 0:
+            raise ValueError("render_shaded_window needs a non-empty (H, W) array of a raster dtype")
+        if isinstance(out, np.ndarray):
+            h, w = (int(v) for v in out_shape)
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("the destination buffer must be a writable contiguous uint8 array")
+            rs = w * int(channels) if dst_row_stride is None else int(dst_row_stride)
+            if out.size < (h - 1) * rs + w * int(channels):
+                raise ValueError("the destination buffer is shorter than the destination")
+        else:
+            h, w = (int(v) for v in out)
+            rs = w * int(channels)
+            out = np.zeros((max(h, 0), max(w, 0), max(int(channels), 0)), dtype=np.uint8)
+        rp, keep = self._render_params(lo, hi, lut, nodata_rgba, channels)
+        sp, keep2 = self._shade_params(light, kx, ky, table)
+        sd = self.make_raster_desc(a.shape[0], a.shape[1], a.dtype)
+        dd = self.make_raster_desc(h, w, np.uint8, row_stride=rs)
+        m = self._window_map(rect, 0.0)
+        self._check(self.lib.frs_render_shaded_window(
+            self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), ctypes.byref(m),
+            self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(rp), ctypes.byref(sp)))
+        del keep, keep2
         return out
 
     # ---- band statistics and histogram

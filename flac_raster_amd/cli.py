@@ -526,7 +526,27 @@ def stats(
         raise typer.Exit(1)
 
 
-@app.command()
+def _hillshade_value_follows(args, i) -> bool:
+    """Is args[i + 1] the AZ,ALT of the --hillshade at args[i]?  It is when it begins like a number."""
+    import re
+    return i + 1 < len(args) and re.match(r"[-+]?(\d|\.\d|nan|inf)", args[i + 1], re.IGNORECASE) is not None
+
+
+class _RenderCommand(typer.core.TyperCommand):
+    """`--hillshade` may stand alone: the default azimuth and altitude are put behind it before the options are parsed
+    (an option of the parser takes a value or none, not either)."""
+
+    def parse_args(self, ctx, args):
+        from .render import DEFAULT_HILLSHADE
+        out = []
+        for i, a in enumerate(args):
+            out.append(a)
+            if a == "--hillshade" and not _hillshade_value_follows(args, i):
+                out.append("%r,%r" % DEFAULT_HILLSHADE)
+        return super().parse_args(ctx, out)
+
+
+@app.command(cls=_RenderCommand)
 def render(
     flac_url: str = typer.Argument(..., help="Streaming FLAC file (local path or HTTP URL)"),
     bbox: Optional[str] = typer.Option(None, "--bbox", "-b", help="Bounding box as 'xmin,ymin,xmax,ymax' (default: "
@@ -549,6 +569,17 @@ def render(
                                                                 "'none' to render without one"),
     channels: int = typer.Option(4, "--channels", help="1 (grey), 2 (grey, alpha) or 4 (R, G, B, A)"),
     force: bool = typer.Option(False, "--force", help="Overwrite the output file"),
+    hillshade: Optional[str] = typer.Option(None, "--hillshade", help="Shade the image by the relief: the light's "
+                                            "azimuth (clockwise from north) and altitude in degrees as 'AZ,ALT', or "
+                                            "alone for 315,45.  Horn's gradient on the output grid, with the output "
+                                            "pixel's size in the units of the file's coordinates: a geographic CRS "
+                                            "(degrees against metres) needs --z-factor, nothing is guessed"),
+    z_factor: Optional[float] = typer.Option(None, "--z-factor", help="Heights are multiplied by F before the slope is "
+                                                                      "taken (> 0; needs --hillshade)"),
+    shade_strength: Optional[float] = typer.Option(None, "--shade-strength", help="0 (none) .. 1 (full, the default) "
+                                                                                  "(needs --hillshade)"),
+    shade_only: bool = typer.Option(False, "--shade-only", help="The shade alone, in grey: no stretch, colour ramp or "
+                                                                "statistics (needs --hillshade)"),
 ):
     """Render a window of a streaming file as a stretched 8-bit colour image on the GPU (extension)"""
     from . import render as rn
@@ -585,6 +616,30 @@ def render(
         rn.parse_stretch(stretch)
     except ValueError as e:
         fail(str(e))
+    shade_kw = {}
+    if hillshade is None:
+        for name, v in (("--z-factor", z_factor), ("--shade-strength", shade_strength),
+                        ("--shade-only", shade_only or None)):
+            if v is not None:
+                fail(f"{name} needs --hillshade")
+    else:
+        import math
+        try:
+            shade_kw["hillshade"] = rn.parse_hillshade(hillshade)
+        except ValueError as e:
+            fail(str(e))
+        if z_factor is not None:
+            if not (math.isfinite(z_factor) and z_factor > 0):
+                fail(f"--z-factor must be a finite number > 0, got {z_factor}")
+            shade_kw["z_factor"] = z_factor
+        if shade_strength is not None:
+            if not 0 <= shade_strength <= 1:
+                fail(f"--shade-strength must lie in [0, 1], got {shade_strength}")
+            shade_kw["shade_strength"] = shade_strength
+        if shade_only:
+            if colormap != "gray" or stretch != rn.DEFAULT_STRETCH or stats_from != "auto":
+                fail("--shade-only renders the shade alone: it excludes --colormap, --stretch and --stats-from")
+            shade_kw["shade_only"] = True
     nd = "index" if nodata is None else _nodata_option(nodata, "none")
     coords = None
     if bbox is not None:
@@ -614,7 +669,7 @@ def render(
             size = rn.max_size_shape(coords[2] - coords[0], coords[3] - coords[1], max_size)
         img, tr = streaming.render_window(flac_url, coords, size[0], size[1], stretch=stretch, stats_from=stats_from,
                                           colormap=ramp, gamma=gamma, transfer=transfer, resampling=resampling,
-                                          level=level, nodata=nd, channels=channels)
+                                          level=level, nodata=nd, channels=channels, **shade_kw)
         if suffix == ".png":
             from .png import write_png
             write_png(output, img)
@@ -623,7 +678,12 @@ def render(
             epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
             geotiff.write(output, img.transpose(2, 0, 1), transform=geotiff.Affine(*tr[:6]), epsg=epsg,
                           alpha=channels > 1)
-        typer.echo(f"SUCCESS: rendered {size[0]}x{size[1]}x{channels} ({stretch}, {resampling}) -> {output}")
+        what = f"{stretch}, {resampling}"
+        if shade_kw:
+            az, alt = shade_kw["hillshade"]
+            what = (f"shade only, {resampling}" if shade_only else what) + f", hillshade {az:g},{alt:g}"
+            what += f" z-factor {shade_kw.get('z_factor', 1.0):g} strength {shade_kw.get('shade_strength', 1.0):g}"
+        typer.echo(f"SUCCESS: rendered {size[0]}x{size[1]}x{channels} ({what}) -> {output}")
     except (KeyError, LookupError, ValueError) as e:
         typer.echo(f"Error: {e}", err=True)
         raise typer.Exit(1)

@@ -192,6 +192,12 @@ int downsample_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src, cons
 int check_window_desc(frs_ctx *ctx, const frs_raster_desc *d);
 int check_window_map(frs_ctx *ctx, const frs_window_map *map, int32_t mode, bool with_fill);
 int64_t window_extent(const frs_raster_desc *d);
+// The checks frs_render_window* and frs_render_shaded_window* share (frs_render.hip): every argument of a render; bytes
+// from a uint8 destination's origin to the end of its last row of C channels (-1: that does not fit 63 bits).
+int check_render_args(frs_ctx *ctx, const frs_raster_desc *src, const void *sp, const frs_raster_desc *dst,
+                      const void *dp, const frs_window_map *map, int32_t mode, const double *nodata,
+                      const frs_render_params *rp);
+int64_t render_dst_bytes(const frs_raster_desc *d, int C);
 // May `nd` be the nodata value of a raster of dtype `dt` (frs_nodata.h: nd_representable)?
 bool nodata_ok(int dt, double nd);
 

@@ -110,7 +110,7 @@ static int render_job(frs_ctx *ctx, const frs_raster_desc *s, const void *src_de
 }
 
 // bytes from the destination's origin to the end of its last row, or -1 when that does not fit 63 bits
-static int64_t render_dst_bytes(const frs_raster_desc *d, int C) {
+int64_t render_dst_bytes(const frs_raster_desc *d, int C) {
     int64_t x, y;
     if (__builtin_mul_overflow(d->height - 1, d->row_stride, &y) || __builtin_mul_overflow(d->width, (int64_t)C, &x) ||
         __builtin_add_overflow(x, y, &x))
@@ -118,10 +118,11 @@ static int64_t render_dst_bytes(const frs_raster_desc *d, int C) {
     return x;
 }
 
-// argument checks of frs_render_window*, before anything is sized, copied or launched
-static int check_render_args(frs_ctx *ctx, const frs_raster_desc *src, const void *sp, const frs_raster_desc *dst,
-                             const void *dp, const frs_window_map *map, int32_t mode, const double *nodata,
-                             const frs_render_params *rp) {
+// argument checks of frs_render_window* (and of frs_render_shaded_window*, frs_shade.hip), before anything is sized,
+// copied or launched
+int check_render_args(frs_ctx *ctx, const frs_raster_desc *src, const void *sp, const frs_raster_desc *dst,
+                      const void *dp, const frs_window_map *map, int32_t mode, const double *nodata,
+                      const frs_render_params *rp) {
     if (int rc = check_window_desc(ctx, src)) return rc;
     if (int rc = check_window_desc(ctx, dst)) return rc;
     if (src->nbands != 1 || dst->nbands != 1) { ctx->err = "render: nbands must be 1"; return FRS_E_ARG; }

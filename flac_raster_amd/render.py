@@ -217,6 +217,59 @@ def build_lut(colormap="gray", n: int = 256, gamma: float = 1.0, transfer: str =
     return lut
 
 
+# ------------------------------------------------------------------------------------------------ hillshade
+DEFAULT_HILLSHADE = (315.0, 45.0)  # azimuth clockwise from north, altitude; degrees
+
+
+def light_vector(azimuth_deg: float = 315.0, altitude_deg: float = 45.0) -> Tuple[float, float, float]:
+    """(lx, ly, lz), the unit vector towards the light: east, north, up = sin A cos h, cos A cos h, sin h for the
+    azimuth A clockwise from north and the altitude h above the horizon, both in degrees.  The azimuth is any finite
+    number, the altitude must lie in (0, 90]."""
+    a, h = float(azimuth_deg), float(altitude_deg)
+    if not math.isfinite(a):
+        raise ValueError(f"the azimuth must be finite, got {azimuth_deg}")
+    if not 0 < h <= 90:
+        raise ValueError(f"the altitude must lie in (0, 90], got {altitude_deg}")
+    a, h = math.radians(a), math.radians(h)
+    return math.sin(a) * math.cos(h), math.cos(a) * math.cos(h), math.sin(h)
+
+
+def shade_table(strength: float = 1.0) -> np.ndarray:
+    """The 256 multipliers of the shade levels, uint8: m[k] = 255 (1 - strength + strength (k + 1/2) / 256), computed
+    in exact rationals and rounded half to even.  strength in [0, 1]: 0 gives all 255 (no shading), 1 the full range."""
+    if not (isinstance(strength, (int, float, Fraction)) and 0 <= strength <= 1):
+        raise ValueError(f"the shade strength must lie in [0, 1], got {strength!r}")
+    s = _frac(strength)
+    return np.array([round(255 * (1 - s + s * Fraction(2 * k + 1, 512))) for k in range(256)], dtype=np.uint8)
+
+
+def parse_hillshade(spec) -> Tuple[float, float]:
+    """(azimuth, altitude) from "az,alt" in degrees, the altitude in (0, 90]; ValueError for anything else."""
+    parts = str(spec).split(",")
+    try:
+        az, alt = (float(x) for x in parts)
+    except ValueError:
+        raise ValueError(f"--hillshade takes AZ,ALT in degrees, got {spec!r}") from None
+    if not math.isfinite(az):
+        raise ValueError(f"--hillshade: the azimuth must be finite, got {spec!r}")
+    if not 0 < alt <= 90:
+        raise ValueError(f"--hillshade: the altitude must lie in (0, 90], got {spec!r}")
+    return az, alt
+
+
+def shade_scales(cell_x: float, cell_y: float, z_factor: float = 1.0) -> Tuple[float, float]:
+    """(kx, ky) = (z_factor / (8 cell_x), z_factor / (8 cell_y)) for the ground size of an output pixel."""
+    cx, cy, z = float(cell_x), float(cell_y), float(z_factor)
+    if not (math.isfinite(z) and z > 0):
+        raise ValueError(f"the z-factor must be a finite number > 0, got {z_factor}")
+    if not (cx > 0 and cy > 0):
+        raise ValueError("the cell size must be positive")
+    kx, ky = z / (8.0 * cx), z / (8.0 * cy)
+    if not (math.isfinite(kx) and math.isfinite(ky)):
+        raise ValueError("the z-factor over the cell size is not finite")
+    return kx, ky
+
+
 def max_size_shape(width: float, height: float, max_size: int) -> Tuple[int, int]:
     """(out_w, out_h) that keep the aspect ratio of a width x height box with the longer side max_size: the other is
     rounded (half up) and at least 1."""

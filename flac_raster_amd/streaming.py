@@ -932,7 +932,8 @@ def pick_level_for_scale(index: Dict, scale: float) -> int:
     return best
 
 
-def window_request(index: Dict, bbox: Sequence[float], out_w: int, out_h: int, level: Optional[int] = None) -> Dict:
+def window_request(index: Dict, bbox: Sequence[float], out_w: int, out_h: int, level: Optional[int] = None,
+                   margin: int = 0) -> Dict:
     """What read_window needs to return bbox = [xmin, ymin, xmax, ymax] as out_w x out_h pixels, from the index alone
     (pure).  The transform must be north-up (b = d = 0, a > 0, e < 0), else ValueError.
       scale       max(bbox width in level-0 pixels / out_w, bbox height in level-0 pixels / out_h)
@@ -940,7 +941,10 @@ def window_request(index: Dict, bbox: Sequence[float], out_w: int, out_h: int, l
       window      the level's whole pixels to decode: columns floor(x) - 1 .. ceil(x + width) + 1 and rows floor(y) - 1
                   .. ceil(y + height) + 1 of the bbox's fractional pixel rectangle (x, y, width, height) in that level,
                   clipped to the level's raster.  The one-pixel margin serves bilinear's second tap and absorbs the last
-                  hi(j) landing an ulp past the rectangle.  Width and height are 0 when nothing is left.
+                  hi(j) landing an ulp past the rectangle.  Width and height are 0 when nothing is left.  With
+                  `margin` = m the rectangle is first widened by m output pixels (m * width / out_w, m * height / out_h)
+                  on every side, for a kernel that looks at an output's neighbours (the hillshade); level, rect and
+                  transform are the unwidened box's.
       rect        (x0, y0, width, height): the rectangle relative to the window's origin, as frs_window_map takes it
       frames      the level's index entries whose `window` intersects the window, in index order
       transform   of the result: [(xmax - xmin) / out_w, 0, xmin, 0, -(ymax - ymin) / out_h, ymax]"""
@@ -962,8 +966,16 @@ def window_request(index: Dict, bbox: Sequence[float], out_w: int, out_h: int, l
     W, H = int(li["width"]), int(li["height"])
     x, y = (xmin - c) / a, (ymax - f) / e
     width, height = (xmax - xmin) / a, (ymin - ymax) / e
-    c0, c1 = max(math.floor(x) - 1, 0), min(math.ceil(x + width) + 1, W)
-    r0, r1 = max(math.floor(y) - 1, 0), min(math.ceil(y + height) + 1, H)
+    margin = int(margin)
+    if margin < 0:
+        raise ValueError("margin must be >= 0")
+    if margin:
+        mx, my = margin * (width / out_w), margin * (height / out_h)
+        c0, c1 = max(math.floor(x - mx) - 1, 0), min(math.ceil(x + width + mx) + 1, W)
+        r0, r1 = max(math.floor(y - my) - 1, 0), min(math.ceil(y + height + my) + 1, H)
+    else:
+        c0, c1 = max(math.floor(x) - 1, 0), min(math.ceil(x + width) + 1, W)
+        r0, r1 = max(math.floor(y) - 1, 0), min(math.ceil(y + height) + 1, H)
     if c1 <= c0 or r1 <= r0:
         c1, r1 = c0, r0
     frames = []
@@ -1095,8 +1107,16 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
                   stretch: str = "percentile:2,98", stats_from: str = "auto", colormap="gray", gamma: float = 1.0,
                   transfer: str = "linear", lut_size: Optional[int] = None, resampling: str = "average",
                   level: Optional[int] = None, nodata="index", channels: int = 4, nodata_rgba=(0, 0, 0, 0),
-                  ctx: Optional[Context] = None):
+                  ctx: Optional[Context] = None, hillshade: Optional[Sequence[float]] = None, z_factor: float = 1.0,
+                  shade_strength: float = 1.0, shade_only: bool = False):
     """Extension: bbox = [xmin, ymin, xmax, ymax] of band 1 as a stretched 8-bit image of exactly out_w x out_h pixels.
+    With hillshade = (azimuth, altitude) in degrees the image is shaded by frs_render_shaded_window_device: Horn's
+    gradient on the output grid, the output pixel's ground size (xmax - xmin) / out_w by (ymax - ymin) / out_h, heights
+    multiplied by z_factor, the colours scaled by render.shade_table(shade_strength).  The decoded window then reaches
+    one output pixel beyond the box (window_request's margin), so that neighbouring map tiles shade identically along
+    their seam.  A geographic CRS (degrees against metres) needs a z_factor from the caller; nothing is guessed.
+    shade_only renders the shade alone: a one-entry white table over a fixed range, no statistics pass (stretch,
+    colormap and stats_from are not looked at).
     It is read_window up to the decoded device window (window_request, fetch_tiles, decode_into_window); then
     frs_render_window_device (the definition in include/flac_raster_amd.h) resamples the window onto the requested
     grid, maps every value to a colour and writes interleaved uint8 pixels, and only those out_h * out_w * channels
@@ -1124,6 +1144,21 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
     channels = int(channels)
     if channels not in (1, 2, 4):
         raise ValueError(f"channels must be 1, 2 or 4; got {channels}")
+    shade = None
+    if hillshade is None:
+        if shade_only or z_factor != 1.0 or shade_strength != 1.0:
+            raise ValueError("z_factor, shade_strength and shade_only need hillshade")
+    else:
+        xmin, ymin, xmax, ymax = (float(v) for v in bbox)
+        azimuth, altitude = hillshade
+        if int(out_w) < 1 or int(out_h) < 1:
+            raise ValueError("the output size must be at least 1 x 1")
+        shade = (rn.light_vector(azimuth, altitude),
+                 *rn.shade_scales((xmax - xmin) / int(out_w), (ymax - ymin) / int(out_h), z_factor),
+                 rn.shade_table(shade_strength))
+    if shade_only:
+        stretch, colormap, gamma, transfer, lut_size = "range:0,1", [(0, 255, 255, 255), (1, 255, 255, 255)], 1.0, \
+            "linear", 1
     kind, _ = rn.parse_stretch(stretch)
     lut = rn.build_lut(colormap, rn.default_lut_size(gamma, transfer) if lut_size is None else lut_size, gamma,
                        transfer)
@@ -1138,7 +1173,8 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
         except (LookupError, ValueError):
             if stats_from == "file":
                 raise
-    req = window_request(index, bbox, out_w, out_h, level)
+    req = window_request(index, bbox, out_w, out_h, level) if shade is None else \
+        window_request(index, bbox, out_w, out_h, level, margin=1)
     out_w, out_h = req["out_w"], req["out_h"]
     if not req["frames"]:
         out = np.empty((out_h, out_w, channels), dtype=np.uint8)
@@ -1164,8 +1200,13 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
             stats = _device_statistics(ctx, wdev.ptr, sd, nd, RENDER_WINDOW_BINS)[0]
         lo, hi = rn.stretch_limits(stats, stretch)
         dst = ctx.alloc(out_h * out_w * channels)
-        ctx.render_window_device(wdev.ptr, sd, dst.ptr, out_h, out_w, req["rect"], resampling, lo, hi, lut,
-                                 nodata_rgba=packed, channels=channels, nodata=nd)
+        if shade is None:
+            ctx.render_window_device(wdev.ptr, sd, dst.ptr, out_h, out_w, req["rect"], resampling, lo, hi, lut,
+                                     nodata_rgba=packed, channels=channels, nodata=nd)
+        else:
+            ctx.render_shaded_window_device(wdev.ptr, sd, dst.ptr, out_h, out_w, req["rect"], resampling, lo, hi,
+                                            lut, shade[0], shade[1], shade[2], shade[3], nodata_rgba=packed,
+                                            channels=channels, nodata=nd)
         out = np.empty((out_h, out_w, channels), dtype=np.uint8)
         dst.download(out=out)
     finally:

@@ -438,6 +438,45 @@ int frs_render_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_
                       void *dst_host, const frs_window_map *map, int32_t mode, const double *nodata,
                       const frs_render_params *render);
 
+/* The render above with hillshade: Horn's 3 x 3 gradient taken on the OUTPUT grid, a Lambertian shade, and the colour
+ * scaled by a 256-entry table.  csrc/frs_shade.h holds the arithmetic for host and device; the definition is this
+ * library's own (the gradient is Horn's, as in gdaldem hillshade, but no parity with GDAL is claimed).  Every step is
+ * one IEEE fp64 operation.  src, dst, map, mode, nodata and render mean what they mean in frs_render_window*.
+ *   samples    For an output pixel (x, y), z[dy][dx], dx, dy in {-1, 0, +1}, is the resampled value at output position
+ *              (x + dx, y + dy) under the call's own mapping, converted to double.  Positions -1 and width / height are
+ *              included: they are plain arithmetic in the position, so the apron comes from the raster, not from
+ *              replication (two neighbouring map tiles shade identically along their seam when the source reaches one
+ *              output pixel beyond the box).  A sample has no data where frs_render_window* finds none (NaN included;
+ *              +-inf are data).  A centre without data gives nodata_rgba; a neighbour without data is replaced by the
+ *              centre's value.
+ *   gradient   Rows grow southwards; 2z is z + z, every sum left to right as written:
+ *              gx = (z[-1][+1] + (z[0][+1] + z[0][+1]) + z[+1][+1]) - (z[-1][-1] + (z[0][-1] + z[0][-1]) + z[+1][-1])
+ *              gy = (z[+1][-1] + (z[+1][0] + z[+1][0]) + z[+1][+1]) - (z[-1][-1] + (z[-1][0] + z[-1][0]) + z[-1][+1])
+ *              p = gx * kx, q = gy * ky, with kx = z_factor / (8 cell_x), ky = z_factor / (8 cell_y) computed by the
+ *              caller from the ground size of an OUTPUT pixel.
+ *   shade      (lx, ly, lz) is the unit vector towards the light: sin A cos h, cos A cos h, sin h for the azimuth A
+ *              clockwise from north and the altitude h (the trigonometry is the caller's).
+ *              num = (lz - p * lx) + q * ly;  den = sqrt((1.0 + p * p) + q * q), correctly rounded;  s = num / den;
+ *              k = 0 when s > 0 is false (NaN included), otherwise min((int)floor(s * 256.0), 255).
+ *   colour     rgba = lut[index of the centre value], the plain render's colour; m = table[k]; R, G and B each become
+ *              (c * m + 127) / 255 in integer arithmetic, A is untouched.  C = 1 stores the shaded R, C = 2 the shaded
+ *              R and A, C = 4 R, G, B, A.  With m = 255 the pixel is frs_render_window*'s.
+ * FRS_E_ARG, before anything is sized, copied or launched: everything frs_render_window* rejects, a null `shade` or
+ * table, and any of the five doubles not finite.  The store contract is frs_render_window*'s.  Synchronous on the
+ * context stream; profile entry "render_shaded".  frs_render_shaded_window takes host rasters, staged like
+ * frs_render_window's. */
+typedef struct {
+    double lx, ly, lz, kx, ky;
+    const uint8_t *table; /* host: 256 bytes */
+} frs_shade_params;
+int frs_render_shaded_window_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                                    const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map, int32_t mode,
+                                    const double *nodata, const frs_render_params *render,
+                                    const frs_shade_params *shade);
+int frs_render_shaded_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host,
+                             const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
+                             const double *nodata, const frs_render_params *render, const frs_shade_params *shade);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
