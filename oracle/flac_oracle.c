@@ -954,8 +954,20 @@ static uint32_t br_unary(br_t *b) {
 
 /* Decode the frames that follow a stream header; returns samples per channel decoded, or <0 on error.
  * out: interleaved int32, capacity cap_samples per channel. */
+/* census (test diagnostics): one variable-length int32 record per subframe, frame-major --
+ *   frame, channel, assignment code, block size, type code, order, wasted bits, precision, shift, residual method,
+ *   partition order, ncoef, coefficients..., nparts, per partition the Rice parameter or -1 - raw width of an escape.
+ * CONSTANT / VERBATIM: method and partition order -1, no coefficients, no partitions; FIXED: precision and shift 0.
+ * cs_len receives the ints a complete census takes; ints beyond cs_cap are counted, not written. */
+typedef struct { int32_t *v; int64_t cap, n; } census_t;
+static void cs_put(census_t *c, int64_t v) {
+    if (!c) return;
+    if (c->n < c->cap) c->v[c->n] = (int32_t)v;
+    c->n++;
+}
+
 static int64_t decode_frames_impl(const uint8_t *in, int64_t n, int ch, int bps, int32_t *out, int64_t cap_samples,
-                                  int8_t *ca_out, int64_t ca_cap, int16_t *sf_out, int64_t sf_cap) {
+                                  int8_t *ca_out, int64_t ca_cap, int16_t *sf_out, int64_t sf_cap, census_t *cs) {
     int64_t nsf = 0;
     crc_init();
     int64_t nfr = 0;
@@ -998,15 +1010,20 @@ static int64_t decode_frames_impl(const uint8_t *in, int64_t n, int ch, int bps,
             int w = 0;
             if (br_u(&b, 1)) w = (int)br_unary(&b) + 1;
             sbps -= w;
+            cs_put(cs, nfr - 1); cs_put(cs, c); cs_put(cs, ca); cs_put(cs, bs); cs_put(cs, t);
             if (t == 0) {
                 int64_t v = br_s(&b, sbps);
                 for (int i = 0; i < bs; i++) x[i] = v;
+                cs_put(cs, 0); cs_put(cs, w); cs_put(cs, 0); cs_put(cs, 0); cs_put(cs, -1); cs_put(cs, -1);
+                cs_put(cs, 0); cs_put(cs, 0);
             } else if (t == 1) {
                 for (int i = 0; i < bs; i++) x[i] = br_s(&b, sbps);
+                cs_put(cs, 0); cs_put(cs, w); cs_put(cs, 0); cs_put(cs, 0); cs_put(cs, -1); cs_put(cs, -1);
+                cs_put(cs, 0); cs_put(cs, 0);
             } else if ((t >= 8 && t <= 12) || t >= 32) {
                 int lpc = t >= 32, o = lpc ? t - 31 : t - 8;
                 int64_t q[32];
-                int shift = 0, prec;
+                int shift = 0, prec = 0;
                 for (int i = 0; i < o; i++) x[i] = br_s(&b, sbps);
                 if (lpc) {
                     prec = (int)br_u(&b, 4) + 1;
@@ -1015,6 +1032,10 @@ static int64_t decode_frames_impl(const uint8_t *in, int64_t n, int ch, int bps,
                 }
                 int method = (int)br_u(&b, 2), po = (int)br_u(&b, 4);
                 if (sf_out && nsf < sf_cap) sf_out[nsf] = (int16_t)(t | (po << 8));
+                cs_put(cs, o); cs_put(cs, w); cs_put(cs, prec); cs_put(cs, shift); cs_put(cs, method); cs_put(cs, po);
+                cs_put(cs, lpc ? o : 0);
+                if (lpc) for (int i = 0; i < o; i++) cs_put(cs, q[i]);
+                cs_put(cs, 1 << po);
                 int pb = method == 0 ? 4 : 5, esc = (1 << pb) - 1;
                 int idx = o;
                 for (int p = 0; p < (1 << po); p++) {
@@ -1022,8 +1043,10 @@ static int64_t decode_frames_impl(const uint8_t *in, int64_t n, int ch, int bps,
                     int k = (int)br_u(&b, pb);
                     if (k == esc) {
                         int nb = (int)br_u(&b, 5);
+                        cs_put(cs, -1 - nb);
                         for (int i = 0; i < ns; i++) x[idx + i] = nb ? br_s(&b, nb) : 0;
                     } else {
+                        cs_put(cs, k);
                         for (int i = 0; i < ns; i++) {
                             uint32_t qq = br_unary(&b);
                             uint32_t u = (qq << k) | (uint32_t)(k ? br_u(&b, k) : 0);
@@ -1077,20 +1100,29 @@ static int64_t decode_frames_impl(const uint8_t *in, int64_t n, int ch, int bps,
 }
 
 int64_t orc_decode_frames(const uint8_t *in, int64_t n, int ch, int bps, int32_t *out, int64_t cap_samples) {
-    return decode_frames_impl(in, n, ch, bps, out, cap_samples, NULL, 0, NULL, 0);
+    return decode_frames_impl(in, n, ch, bps, out, cap_samples, NULL, 0, NULL, 0, NULL);
 }
 
 /* as orc_decode_frames, and every subframe's type code (| residual partition order << 8 for FIXED / LPC) into
  * sf_out, frame-major (test diagnostics: the compression level's predictor and partition limits) */
 int64_t orc_decode_frames_sf(const uint8_t *in, int64_t n, int ch, int bps, int32_t *out, int64_t cap_samples,
                              int16_t *sf_out, int64_t sf_cap) {
-    return decode_frames_impl(in, n, ch, bps, out, cap_samples, NULL, 0, sf_out, sf_cap);
+    return decode_frames_impl(in, n, ch, bps, out, cap_samples, NULL, 0, sf_out, sf_cap, NULL);
 }
 
 /* as orc_decode_frames, and the channel assignment code of every frame into ca_out (test diagnostics) */
 int64_t orc_decode_frames_ca(const uint8_t *in, int64_t n, int ch, int bps, int32_t *out, int64_t cap_samples,
                              int8_t *ca_out, int64_t ca_cap) {
-    return decode_frames_impl(in, n, ch, bps, out, cap_samples, ca_out, ca_cap, NULL, 0);
+    return decode_frames_impl(in, n, ch, bps, out, cap_samples, ca_out, ca_cap, NULL, 0, NULL);
+}
+
+/* as orc_decode_frames, and the census of every subframe's coded form (layout at census_t) */
+int64_t orc_decode_frames_census(const uint8_t *in, int64_t n, int ch, int bps, int32_t *out, int64_t cap_samples,
+                                 int32_t *cs_out, int64_t cs_cap, int64_t *cs_len) {
+    census_t cs = {cs_out, cs_cap, 0};
+    int64_t r = decode_frames_impl(in, n, ch, bps, out, cap_samples, NULL, 0, NULL, 0, &cs);
+    *cs_len = cs.n;
+    return r;
 }
 
 /* ------------------------------------------------------------------ streaming tiler (cli.py:690-763) */

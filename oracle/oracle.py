@@ -52,6 +52,8 @@ def lib():
         L.orc_decode_frames_ca.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64]
         L.orc_decode_frames_sf.restype = i64
         L.orc_decode_frames_sf.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64]
+        L.orc_decode_frames_census.restype = i64
+        L.orc_decode_frames_census.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64, ctypes.POINTER(i64)]
         L.orc_encode_tiles.restype = i64
         L.orc_encode_tiles.argtypes = [vp, i32, i64, i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, i32]
         L.orc_normalize_spatial.restype = i32
@@ -163,6 +165,40 @@ def subframe_types(data: bytes, channels: int, bps: int, max_samples: int, block
     t = sf & 0xFF
     po = np.where((t >= 8), sf >> 8, -1)
     return np.stack([t, po], axis=1)
+
+
+def subframe_census(data: bytes, channels: int, bps: int, max_samples: int) -> list:
+    """The coded form of every subframe, frame-major, one dict each: frame, channel, assignment (the frame's
+    channel-assignment code), blocksize, type (the code of subframe_types), kind ("constant" | "verbatim" | "fixed" |
+    "lpc"), order, wasted, precision / shift / coefs (LPC; 0, 0, () otherwise), method (0: 4-bit Rice parameters,
+    1: 5-bit; -1 without a residual), porder (-1 without a residual) and params: per partition the Rice parameter, or
+    ("esc", raw width) for an escape partition."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    out = np.empty((max_samples, channels), dtype=np.int32)
+    need = ctypes.c_int64(0)
+    cs = np.empty(1 << 16, dtype=np.int32)
+    for _ in range(2):
+        r = lib().orc_decode_frames_census(_ptr(buf), len(buf), channels, bps, _ptr(out), max_samples, _ptr(cs), len(cs),
+                                           ctypes.byref(need))
+        if r < 0:
+            raise RuntimeError(f"oracle decode error {r}")
+        if need.value <= len(cs):
+            break
+        cs = np.empty(need.value, dtype=np.int32)
+    v, at, subs = cs[:need.value].tolist(), 0, []
+    while at < len(v):
+        frame, channel, ca, bs, t, order, wasted, prec, shift, method, po, ncoef = v[at:at + 12]
+        at += 12
+        coefs = tuple(v[at:at + ncoef])
+        at += ncoef
+        nparts = v[at]
+        params = [k if k >= 0 else ("esc", -1 - k) for k in v[at + 1:at + 1 + nparts]]
+        at += 1 + nparts
+        kind = "constant" if t == 0 else "verbatim" if t == 1 else "fixed" if t < 32 else "lpc"
+        subs.append(dict(frame=frame, channel=channel, assignment=ca, blocksize=bs, type=t, kind=kind, order=order,
+                         wasted=wasted, precision=prec, shift=shift, coefs=coefs, method=method, porder=po,
+                         params=params))
+    return subs
 
 
 def denormalize_i16(pcm: np.ndarray, dmin: float, dmax: float, dtype, pcm_bps: int = 16) -> np.ndarray:

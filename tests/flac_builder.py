@@ -149,7 +149,7 @@ def _write_residual(bw: BitWriter, res: np.ndarray, bs: int, order: int, sub: Su
     if params is None or isinstance(params, (int, tuple)):
         params = [params] * (1 << po)
     assert len(params) == 1 << po
-    at = 0
+    at, written = 0, []
     for p, par in enumerate(params):
         ns = (bs >> po) - (order if p == 0 else 0)
         r = res[at:at + ns]
@@ -160,6 +160,7 @@ def _write_residual(bw: BitWriter, res: np.ndarray, bs: int, order: int, sub: Su
             assert 0 <= nb <= 31 and _signed_width(r) <= nb, "escape width too narrow"
             bw.put(esc, pb)
             bw.put(nb, 5)
+            written.append(("esc", nb))
             if nb:
                 bw.put_array(r.astype(np.uint64) & np.uint64((1 << nb) - 1), np.full(ns, nb))
             continue
@@ -169,6 +170,7 @@ def _write_residual(bw: BitWriter, res: np.ndarray, bs: int, order: int, sub: Su
             par = int(np.argmin(cost))
         assert 0 <= par < esc
         bw.put(par, pb)
+        written.append(par)
         k = np.uint64(par)
         vals = np.zeros(2 * ns, dtype=np.uint64)
         widths = np.empty(2 * ns, dtype=np.int64)
@@ -177,9 +179,11 @@ def _write_residual(bw: BitWriter, res: np.ndarray, bs: int, order: int, sub: Su
         widths[1::2] = par + 1
         bw.put_array(vals, widths)
     assert at == res.size
+    return written
 
 
 def _write_subframe(bw: BitWriter, x: np.ndarray, sbps: int, sub: Sub):
+    """-> the partitions' parameters as written (a Rice parameter or ("esc", width) each; [] without a residual)"""
     x = np.asarray(x, dtype=np.int64)
     bs = len(x)
     w = sub.wasted
@@ -206,7 +210,7 @@ def _write_subframe(bw: BitWriter, x: np.ndarray, sbps: int, sub: Sub):
         o = sub.order
         assert 0 <= o <= 4 and o <= bs
         raw(x[:o])
-        _write_residual(bw, residuals(x, FIXED_COEFS[o], 0), bs, o, sub)
+        return _write_residual(bw, residuals(x, FIXED_COEFS[o], 0), bs, o, sub)
     elif sub.kind == "lpc":
         o, prec = sub.order, sub.precision
         assert 1 <= o <= 32 and o <= bs and len(sub.coefs) == o and 1 <= prec <= 15 and 0 <= sub.shift <= 31
@@ -216,18 +220,20 @@ def _write_subframe(bw: BitWriter, x: np.ndarray, sbps: int, sub: Sub):
         bw.put(sub.shift, 5)
         for c in sub.coefs:
             bw.put(c & ((1 << prec) - 1), prec)
-        _write_residual(bw, residuals(x, sub.coefs, sub.shift), bs, o, sub)
+        return _write_residual(bw, residuals(x, sub.coefs, sub.shift), bs, o, sub)
     else:
         raise ValueError(sub.kind)
+    return []
 
 
 def frame(channels: Sequence[np.ndarray], subs: Sequence[Sub], frame_no: int, bps: int, *, chass: Optional[int] = None,
           bs_code: Optional[int] = None, sr_code: int = 9, sr_extra: Optional[int] = None,
-          ss_code: Optional[int] = None) -> bytes:
+          ss_code: Optional[int] = None, written: Optional[list] = None) -> bytes:
     """One frame.  channels: the samples per channel (for chass 8..10: left and right; the writer forms side, of
     bps + 1 bits, and mid).  bs_code: a table code, 6 / 7 for the explicit 8- / 16-bit forms, None = the table code
     where one exists, else the narrowest explicit form.  sr_code 12..14 carry sr_extra (kHz in 8 bits, Hz in 16,
-    Hz / 10 in 16).  ss_code: None = the code of bps, 0 = "from the stream"."""
+    Hz / 10 in 16).  ss_code: None = the code of bps, 0 = "from the stream".  written: a list that receives, per subframe,
+    (the assignment code, the Sub, its partitions' parameters as written)."""
     ch = [np.asarray(c, dtype=np.int64) for c in channels]
     bs = len(ch[0])
     assert all(len(c) == bs for c in ch) and 1 <= bs <= 65536 and len(subs) == len(ch)
@@ -268,7 +274,9 @@ def frame(channels: Sequence[np.ndarray], subs: Sequence[Sub], frame_no: int, bp
             ch, widths = [(left + right) >> 1, side], [bps, bps + 1]
     bw = BitWriter()
     for x, sbps, sub in zip(ch, widths, subs):
-        _write_subframe(bw, x, sbps, sub)
+        params = _write_subframe(bw, x, sbps, sub)
+        if written is not None:
+            written.append((chass, sub, params))
     body = bytes(hdr) + bw.to_bytes()
     return body + crc16(body).to_bytes(2, "big")
 
@@ -276,13 +284,16 @@ def frame(channels: Sequence[np.ndarray], subs: Sequence[Sub], frame_no: int, bp
 @dataclass
 class Stream:
     """Frames of one stream with the samples that went in (pcm: [N, channels] int64) and, per subframe in frame-major
-    order, the forced (type code, partition order; -1 for CONSTANT / VERBATIM)."""
+    order, the forced (type code, partition order; -1 for CONSTANT / VERBATIM).  layout: per subframe in the same order,
+    (assignment code, the Sub it was written from, its partitions' parameters as written: where the Sub left a Rice
+    parameter or an escape width open, the writer's choice)."""
     data: bytes
     pcm: np.ndarray
     bps: int
     blocksize: int
     forced: np.ndarray
     name: str = ""
+    layout: list = field(default_factory=list)
 
     @property
     def channels(self) -> int:
@@ -296,18 +307,18 @@ class Stream:
 def stream_from_frames(frames, bps: int, blocksize: int, name: str = "", **hdr) -> Stream:
     """frames: (samples [n] or [n, C], list of Sub per channel[, dict of frame() header arguments]) per frame, numbered
     from 0; every frame but the last has `blocksize` samples.  hdr: header arguments for every frame."""
-    out, forced, blocks = bytearray(), [], []
+    out, forced, blocks, layout = bytearray(), [], [], []
     for f, fr in enumerate(frames):
         blk = np.asarray(fr[0], dtype=np.int64)
         if blk.ndim == 1:
             blk = blk[:, None]
         subs, kw = fr[1], (fr[2] if len(fr) > 2 else {})
         assert len(blk) == blocksize or (f == len(frames) - 1 and 0 < len(blk) < blocksize)
-        out += frame([blk[:, c] for c in range(blk.shape[1])], subs, f, bps, **{**hdr, **kw})
+        out += frame([blk[:, c] for c in range(blk.shape[1])], subs, f, bps, written=layout, **{**hdr, **kw})
         forced += [(s.type_code, s.porder if s.kind in ("fixed", "lpc") else -1) for s in subs]
         blocks.append(blk)
     return Stream(bytes(out), np.concatenate(blocks), bps, blocksize,
-                  np.array(forced, dtype=np.int64).reshape(-1, 2), name)
+                  np.array(forced, dtype=np.int64).reshape(-1, 2), name, layout)
 
 
 def stream(pcm: np.ndarray, bps: int, blocksize: int, layout, name: str = "", **hdr) -> Stream:

@@ -62,6 +62,87 @@ def test_oracle_decodes_known_samples(name):
     assert np.array_equal(O.subframe_types(s.data, s.channels, s.bps, n, s.blocksize), s.forced)
 
 
+@pytest.mark.parametrize("name", list(L.STREAMS))
+def test_census_reports_the_forced_layout(name):
+    """O.subframe_census against what the writer was told to write, field by field, for every subframe: type, order,
+    wasted bits, LPC precision, shift and coefficients, residual method, partition order, every partition's Rice
+    parameter or escape width, the frame's assignment code, frame and channel numbers and the block size."""
+    s = L.get(name)
+    n = len(s.pcm)
+    cen = O.subframe_census(s.data, s.channels, s.bps, n)
+    assert len(cen) == len(s.layout) == len(s.forced)
+    bad = []
+    for i, (c, (chass, sub, params)) in enumerate(zip(cen, s.layout)):
+        f = i // s.channels
+        resid = sub.kind in ("fixed", "lpc")
+        lpc = sub.kind == "lpc"
+        want = dict(frame=f, channel=i % s.channels, assignment=chass, blocksize=min(s.blocksize, n - f * s.blocksize),
+                    type=sub.type_code, kind=sub.kind, order=sub.order if resid else 0, wasted=sub.wasted,
+                    precision=sub.precision if lpc else 0, shift=sub.shift if lpc else 0,
+                    coefs=tuple(int(q) for q in sub.coefs) if lpc else (), method=sub.method if resid else -1,
+                    porder=sub.porder if resid else -1, params=list(params))
+        if c != want:
+            bad.append((i, {k: (c[k], want[k]) for k in want if c[k] != want[k]}))
+    assert not bad, bad[:5]
+
+
+def test_census_pin_covers_the_rare_forms():
+    """The streams the pin above runs on do hold what the encoder never emits: escape partitions (width 0 too), 5-bit
+    parameters up to 30, LPC orders above 8, partition orders 6, 7 and 8, shifts 0 and 15, both coefficient extremes,
+    wasted bits on every subframe kind and all four two-channel assignment codes."""
+    subs = [(chass, sub, params) for name in L.STREAMS for chass, sub, params in L.get(name).layout]
+    escapes = {p[1] for _, _, params in subs for p in params if isinstance(p, tuple)}
+    assert 0 in escapes and len(escapes) > 3
+    assert {14, 15, 16, 30} <= {p for _, s, params in subs if s.method == 1 for p in params if not isinstance(p, tuple)}
+    assert {9, 12, 32} <= {s.order for _, s, _ in subs if s.kind == "lpc"}
+    assert {0, 1, 2, 3, 4, 5, 6, 7, 8} <= {s.porder for _, s, _ in subs if s.kind in ("fixed", "lpc")}
+    assert {0, 15} <= {s.shift for _, s, _ in subs if s.kind == "lpc"}
+    assert {-16384, 16383} <= {q for _, s, _ in subs if s.kind == "lpc" for q in s.coefs}
+    assert {"constant", "verbatim", "fixed", "lpc"} == {s.kind for _, s, _ in subs if s.wasted}
+    assert {1, 8, 9, 10} <= {chass for chass, _, _ in subs}
+
+
+def _golden_streams(golden):
+    """(name, channels, bps, frames) of sample_rgb.flac (one 16-bit stream after an 86-byte header) and of the 32-bit
+    tile streams of sample_dem.flac that begin with a bare 86-byte header (every stream but the first, whose header
+    carries the tags)."""
+    yield "sample_rgb", 3, 16, (golden / "sample_rgb.flac").read_bytes()[86:]
+    dem = (golden / "sample_dem.flac").read_bytes()
+    starts = [i for i in range(1, len(dem)) if dem[i:i + 4] == b"fLaC"] + [len(dem)]
+    assert len(starts) == 4
+    for k in range(3):
+        yield f"sample_dem[{k + 1}]", 1, 32, dem[starts[k] + 86:starts[k + 1]]
+
+
+def test_census_agrees_with_the_older_walkers_on_the_golden_files(golden):
+    """On libFLAC's own output: type and partition order equal subframe_types', the assignment frame_assignments', and
+    the fields hang together (a partition per 2^order, FIXED without LPC fields, 4-bit parameters below 15)."""
+    for name, channels, bps, data in _golden_streams(golden):
+        _census_agrees(name, channels, bps, data)
+
+
+def _census_agrees(name, channels, bps, data):
+    cap = 1 << 22
+    n = len(O.decode_frames(data, channels, bps, cap))
+    cen = O.subframe_census(data, channels, bps, n)
+    types = O.subframe_types(data, channels, bps, n)
+    ca = O.frame_assignments(data, channels, bps, n)
+    assert len(cen) == len(types) > 0
+    assert [(c["type"], c["porder"]) for c in cen] == [tuple(t) for t in types.tolist()]
+    assert [c["assignment"] for c in cen] == [int(ca[c["frame"]]) for c in cen]
+    assert [c["channel"] for c in cen] == [i % channels for i in range(len(cen))]
+    for c in cen:
+        resid = c["kind"] in ("fixed", "lpc")
+        assert len(c["params"]) == (1 << c["porder"] if resid else 0)
+        assert (c["method"] in (0, 1)) == resid
+        if c["kind"] == "lpc":
+            assert len(c["coefs"]) == c["order"] == c["type"] - 31 and 1 <= c["precision"] <= 15
+        else:
+            assert c["coefs"] == () and c["precision"] == 0 and c["shift"] == 0
+        if c["method"] == 0:
+            assert all(isinstance(p, tuple) or p < 15 for p in c["params"])
+
+
 def test_wrapping_lpc_frames_need_64_bits():
     fr = B.wrapping_lpc_frames(3, 64)
     assert np.all(O.decode_frames(fr, 1, 16, 192) == 32767)
