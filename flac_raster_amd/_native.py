@@ -46,6 +46,7 @@ EXPORTS = (
     "frs_band_stats_device", "frs_band_stats", "frs_band_histogram_device", "frs_band_histogram",
     "frs_render_window_device", "frs_render_window",
     "frs_render_shaded_window_device", "frs_render_shaded_window",
+    "frs_render_composite_window_device", "frs_render_composite_window",
 )
 
 # enum frs_resample
@@ -211,6 +212,12 @@ class ShadeParams(ctypes.Structure):
                 ("ky", ctypes.c_double), ("table", ctypes.c_void_p)]
 
 
+class CompositeParams(ctypes.Structure):
+    """frs_composite_params"""
+    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("lut", ctypes.c_void_p),
+                ("n", ctypes.c_int32), ("nodata_rgba", ctypes.c_uint32)]
+
+
 def pack_rgba(rgba) -> int:
     """nodata_rgba as frs_render_params takes it: R | G << 8 | B << 16 | A << 24, from that integer or from (r, g, b, a)."""
     if isinstance(rgba, (int, np.integer)):
@@ -364,6 +371,9 @@ def load_library(path: Optional[os.PathLike] = None):
         for fn in (L.frs_render_shaded_window_device, L.frs_render_shaded_window):
             fn.restype = i32
             fn.argtypes = rn_args + [ctypes.POINTER(ShadeParams)]
+        for fn in (L.frs_render_composite_window_device, L.frs_render_composite_window):
+            fn.restype = i32
+            fn.argtypes = rw_args + [dp, ctypes.POINTER(CompositeParams)]
         if L.frs_abi_version() != 1:
             raise NativeUnavailable("ABI version mismatch")
         if path is None:
@@ -1017,6 +1027,57 @@ class Context:
             self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), ctypes.byref(m),
             self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(rp), ctypes.byref(sp)))
         del keep, keep2
+        return out
+
+    # ---- three-band composite
+    @staticmethod
+    def _composite_params(lo, hi, lut, nodata_rgba):
+        """(CompositeParams, the array its LUT pointer refers to).  lo and hi are three numbers each (R, G, B); `lut` is
+        uint8 (n, 4), its length the C-ABI's to judge."""
+        t = np.ascontiguousarray(lut, dtype=np.uint8)
+        if t.ndim != 2 or t.shape[1] != 4:
+            raise ValueError("the LUT must be a uint8 array of shape (n, 4)")
+        lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
+        if len(lo3) != 3 or len(hi3) != 3:
+            raise ValueError("a composite takes three lo and three hi values (R, G, B)")
+        d3 = ctypes.c_double * 3
+        return CompositeParams(d3(*lo3), d3(*hi3), t.ctypes.data if t.size else None, int(t.shape[0]),
+                               pack_rgba(nodata_rgba)), t
+
+    def render_composite_window_device(self, src_ptr: int, src_desc: RasterDesc, dst_ptr: int, out_h: int,
+                                       out_w: int, rect, mode, lo, hi, lut, nodata_rgba=0, nodata=None,
+                                       dst_row_stride: Optional[int] = None) -> None:
+        """frs_render_composite_window_device: the rectangle rect = (x0, y0, width, height) of the three-band
+        band-planar device raster at src_ptr (laid out as src_desc, nbands 3), resampled by `mode` onto out_h x out_w
+        pixels and written as interleaved uint8 R, G, B, A at dst_ptr, rows dst_row_stride bytes apart (out_w * 4 by
+        default).  Plane c gives channel c: its value is quantised over [lo[c], hi[c]] as render_window_device does
+        and byte c of that LUT entry is stored; A is 255.  A pixel where any plane has no data takes nodata_rgba."""
+        cp, keep = self._composite_params(lo, hi, lut, nodata_rgba)
+        rs = int(out_w) * 4 if dst_row_stride is None else int(dst_row_stride)
+        dd = self.make_raster_desc(out_h, out_w, np.uint8, row_stride=rs)
+        m = self._window_map(rect, 0.0)
+        self._check(self.lib.frs_render_composite_window_device(
+            self.handle, ctypes.byref(src_desc), ctypes.c_void_p(src_ptr), ctypes.byref(dd), ctypes.c_void_p(dst_ptr),
+            ctypes.byref(m), self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(cp)))
+        del keep
+
+    def render_composite_window(self, a: np.ndarray, rect, out_shape, mode, lo, hi, lut, nodata_rgba=0,
+                                nodata=None) -> np.ndarray:
+        """frs_render_composite_window on a host raster (3, H, W): uint8 (h, w, 4) of out_shape = (h, w); see
+        render_composite_window_device."""
+        a = np.ascontiguousarray(a)
+        if a.ndim != 3 or a.dtype not in DTYPE_CODES or a.size == 0:
+            raise ValueError("render_composite_window needs a non-empty (3, H, W) array of a raster dtype")
+        h, w = (int(v) for v in out_shape)
+        cp, keep = self._composite_params(lo, hi, lut, nodata_rgba)
+        sd = self.make_raster_desc(a.shape[1], a.shape[2], a.dtype, nbands=a.shape[0])
+        dd = self.make_raster_desc(h, w, np.uint8, row_stride=w * 4)
+        out = np.zeros((max(h, 0), max(w, 0), 4), dtype=np.uint8)
+        m = self._window_map(rect, 0.0)
+        self._check(self.lib.frs_render_composite_window(
+            self.handle, ctypes.byref(sd), _p(a), ctypes.byref(dd), _p(out), ctypes.byref(m),
+            self._window_resample_code(mode), self._nodata_arg(nodata), ctypes.byref(cp)))
+        del keep
         return out
 
     # ---- band statistics and histogram

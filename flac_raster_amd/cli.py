@@ -94,7 +94,8 @@ def create_streaming(
                                           "MASTER_ADDR/MASTER_PORT in the environment)"),
     verify: bool = typer.Option(False, "--verify", help="Extension: read the written file back, decode it into one "
                                                         "raster on the GPU and compare it with band 1 of the source "
-                                                        "there (single GPU only); exit status 3 when it differs"),
+                                                        "there, or every stored band with --bands (single GPU only); "
+                                                        "exit status 3 when it differs"),
     overviews: bool = typer.Option(False, "--overviews", help="Extension: append reduced-resolution levels (each a 2x "
                                                               "reduction of the one before, made on the GPU) until "
                                                               "one fits in a single tile (single GPU only)"),
@@ -108,9 +109,26 @@ def create_streaming(
     stats: bool = typer.Option(False, "--stats", help="Extension: compute the band's statistics and a histogram of at "
                                                       "most 256 bins on the GPU and store them in the index (single "
                                                       "GPU only)"),
+    bands: Optional[str] = typer.Option(None, "--bands", help="Extension: store these bands, 'all' or 1-based numbers "
+                                                              "such as 1,2,3 (band 1 must be among them), each as "
+                                                              "mono tiles after the band before it (single GPU "
+                                                              "only; default: band 1 alone)"),
 ):
     """Create Netflix-style streaming FLAC with self-contained tiles"""
     from . import streaming
+    sel = None
+    if bands is not None:
+        if gpus > 1 or distributed:
+            typer.echo("Error: --bands runs on one GPU: it cannot be combined with --gpus > 1 or --distributed",
+                       err=True)
+            raise typer.Exit(1)
+        try:
+            sel = streaming.parse_bands(bands)
+            if sel != "all" and 1 not in sel:
+                raise ValueError(f"--bands must name band 1 (the index's top-level keys are band 1's), got {bands!r}")
+        except ValueError as e:
+            typer.echo(f"Error: {e}", err=True)
+            raise typer.Exit(1)
     if stats and (gpus > 1 or distributed):
         typer.echo("Error: --stats runs on one GPU: it cannot be combined with --gpus > 1 or --distributed", err=True)
         raise typer.Exit(1)
@@ -146,6 +164,14 @@ def create_streaming(
     if output_file.exists() and not force and not distributed:
         typer.echo(f"Error: Output file already exists: {output_file}", err=True)
         raise typer.Exit(1)
+    if sel is not None:  # the one rule that needs the source: checked before anything is written
+        from . import geotiff
+        try:
+            with geotiff.TiffFile(input_file) as tf:
+                sel = streaming.select_bands(sel, tf.count)
+        except ValueError as e:
+            typer.echo(f"Error: --bands: {e}", err=True)
+            raise typer.Exit(1)
     if gpus > 1 and not distributed:
         from .launch import run_ranks
         argv = ["create-streaming", str(input_file), "--output", str(output_file), "--tile-size", str(tile_size),
@@ -164,8 +190,11 @@ def create_streaming(
         else:
             index = streaming.create_streaming(input_file, output_file, tile_size, overviews=overviews,
                                                resampling=resampling, max_levels=overview_levels, nodata=nd,
-                                               stats=stats)
+                                               stats=stats, bands=sel)
         top = max(streaming.overview_levels(index))
+        if sel is not None:
+            typer.echo(f"BANDS: {','.join(str(b) for b in streaming.bands_of(index))} of "
+                       f"{index['bands']['count']}")
         if overviews:
             typer.echo(f"SUCCESS: {output_file} ({len(index['frames'])} tiles, {top} overview levels)")
         else:
@@ -176,7 +205,21 @@ def create_streaming(
             st = index["statistics"]
             typer.echo(f"STATS: valid={st['valid']} nodata={st['nodata_count']} nan={st['nan']} min={st['min']} "
                        f"max={st['max']} mean={st['mean']} std={st['std']}")
-        if verify:
+        if verify and sel is not None:
+            from . import geotiff
+            stored = streaming.bands_of(index)
+            with geotiff.TiffFile(input_file) as tf:
+                for b in stored:  # every stored band, and every level of it, against the source's band
+                    ex = streaming.verify_streaming(output_file, tf.read_rows(bands=[b - 1])[0], band_number=b)
+                    if ex["n_different"] != 0:
+                        differs = True
+                        typer.echo(f"VERIFY: differs (band {b}, n_different={ex['n_different']}, "
+                                   f"max_difference={ex['max_difference']})")
+                        break
+            if not differs:
+                lv = f", levels 0..{ex['levels_checked'] - 1}" if overviews else ""
+                typer.echo(f"VERIFY: lossless (bands {','.join(str(b) for b in stored)}{lv})")
+        elif verify:
             from . import geotiff
             ex = streaming.verify_streaming(output_file, geotiff.read(input_file).data[0])
             differs = ex["n_different"] != 0
@@ -220,10 +263,28 @@ def extract_streaming(
     nodata: Optional[str] = typer.Option(None, "--nodata", help="Extension: override the file's nodata value with a "
                                                                 "number, or 'none' to read without one (default: the "
                                                                 "value in the file's index)"),
+    bands: Optional[str] = typer.Option(None, "--bands", help="Extension: the stored bands to read, 'all' or numbers "
+                                                              "such as 3,1: a multi-band GeoTIFF with --all, --bbox "
+                                                              "--mosaic or --out-size; exactly one band with "
+                                                              "--tile-id, --center, --last or a plain --bbox "
+                                                              "(default: band 1)"),
 ):
     """Extract tiles from Netflix-style streaming FLAC files"""
     from . import streaming
     nd = "index" if nodata is None else _nodata_option(nodata, "none")
+    # --bands: every rule is checked before anything is read
+    sel = None
+    if bands is not None:
+        try:
+            sel = streaming.parse_bands(bands)
+        except ValueError as e:
+            typer.echo(f"Error: {e}", err=True)
+            raise typer.Exit(1)
+        many = all_tiles or (mosaic and bbox is not None) or out_size is not None
+        if not many and (sel == "all" or len(sel) != 1):
+            typer.echo("Error: --tile-id, --center, --last and a plain --bbox read one tile: --bands must name exactly "
+                       "one band there", err=True)
+            raise typer.Exit(1)
     # --out-size: every rule is checked before anything is read
     size = None
     if out_size is None and (resampling is not None or fill is not None):
@@ -283,18 +344,18 @@ def extract_streaming(
             _, index = streaming.read_index(flac_url)
             req = streaming.window_request(index, coords, size[0], size[1], level)
             arr, tr = streaming.read_window(flac_url, coords, size[0], size[1], resampling=resampling, level=level,
-                                            fill=fill, nodata=nd)
+                                            fill=fill, nodata=nd, bands=sel)
             crs = index.get("crs")
             epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
             geotiff.write(output, arr, transform=geotiff.Affine(*tr[:6]), epsg=epsg,
                           nodata=streaming.nodata_in_force(index, nd))
             typer.echo(f"SUCCESS: window {size[0]}x{size[1]} (level {req['level']}, {resampling}) -> {output}")
         elif all_tiles:
-            index = streaming.extract_all(flac_url, output, level=lvl, nodata=nd)
+            index = streaming.extract_all(flac_url, output, level=lvl, nodata=nd, bands=sel)
             typer.echo(f"SUCCESS: Extracted all {len(index['frames'])} tiles to {output}{at}")
         elif mosaic and coords is not None:
             from . import geotiff
-            arr, win, tr = streaming.extract_bbox_mosaic(flac_url, coords, level=lvl)
+            arr, win, tr = streaming.extract_bbox_mosaic(flac_url, coords, level=lvl, bands=sel)
             n, index = streaming.read_index(flac_url)
             crs = index.get("crs")
             epsg = int(crs.split(":")[1]) if crs and crs.upper().startswith("EPSG:") else None
@@ -303,7 +364,7 @@ def extract_streaming(
             typer.echo(f"SUCCESS: mosaic {win} -> {output}{at}")
         else:
             f = streaming.extract_streaming(flac_url, output, bbox=coords, tile_id=tile_id, center=center, last=last,
-                                            level=lvl, nodata=nd)
+                                            level=lvl, nodata=nd, band=1 if sel is None else sel[0])
             typer.echo(f"SUCCESS: Extracted tile {f['frame_id']} to {output}{at}")
     except (KeyError, LookupError, ValueError) as e:
         typer.echo(f"Error: {e}", err=True)
@@ -391,13 +452,18 @@ def info(file_path: str = typer.Argument(..., help="FLAC or TIFF file to inspect
                 con.print(f"  Tile size: {index['tile_size']}")
                 con.print(f"  Tiles (level 0): {len(index['frames'])}")
                 con.print(f"  Overview levels: {len(levels) - 1}")
+                stored = streaming.bands_of(index)
+                of = f" of {index['bands']['count']}" if "bands" in index else ""
+                con.print(f"  Bands stored: {','.join(str(b) for b in stored)}{of}")
                 con.print(f"  CRS: {index.get('crs')}")
                 con.print(f"  Nodata: {index['nodata'] if 'nodata' in index else 'None'}")
                 if "statistics" in index:
                     from .stats import format_band
                     con.print("  Statistics (level 0):")
-                    for line in format_band(1, streaming.index_statistics(index))[1:]:
-                        con.print("  " + line, highlight=False)
+                    for b in stored:
+                        st = streaming.index_statistics(streaming.band_index(index, b))
+                        for line in format_band(b, st)[0 if len(stored) > 1 else 1:]:
+                            con.print("  " + line, highlight=False)
                 con.print(f"  File size: {len(buf) / 1024 / 1024:.2f} MB")
                 return
             except Exception:
@@ -475,9 +541,13 @@ def stats(
                                                  "fits gets one bin per value"),
     percentiles: str = typer.Option("2,50,98", "--percentiles", help="Percentiles to read off the histogram"),
     as_json: bool = typer.Option(False, "--json", help="Print one JSON document"),
+    band: Optional[int] = typer.Option(None, "--band", help="One band (1-based) instead of every band the file holds"),
 ):
     """Band statistics and histogram, computed on the GPU (extension)"""
     from .stats import MAX_BINS
+    if band is not None and band < 1:
+        typer.echo(f"Error: --band numbers start at 1, got {band}", err=True)
+        raise typer.Exit(1)
     # every argument rule is checked before anything is read
     if not 1 <= bins <= MAX_BINS:
         typer.echo(f"Error: --bins must be 1..{MAX_BINS}, got {bins}", err=True)
@@ -503,7 +573,7 @@ def stats(
         raise typer.Exit(1)
     try:
         from .stats import format_band, raster_file_statistics, with_percentiles
-        res = raster_file_statistics(file_path, level=level or 0, nodata=nd, bins=bins)
+        res = raster_file_statistics(file_path, level=level or 0, nodata=nd, bins=bins, band=band)
         res["bands"] = [with_percentiles(b, qs) for b in res["bands"]]
         if as_json:
             from .stats import statistics_to_index
@@ -514,7 +584,7 @@ def stats(
             at = f", level {res['level']}" if suffix == ".flac" else ""
             typer.echo(f"{file_path}: {res['width']} x {res['height']}, {len(res['bands'])} band(s), {res['dtype']}"
                        f"{at}, nodata {res['nodata']}")
-            for i, b in enumerate(res["bands"], 1):
+            for i, b in zip(res["band_numbers"], res["bands"]):
                 for line in format_band(i, b, qs):
                     typer.echo(line)
     except (KeyError, LookupError, ValueError) as e:
@@ -580,6 +650,12 @@ def render(
                                                                                   "(needs --hillshade)"),
     shade_only: bool = typer.Option(False, "--shade-only", help="The shade alone, in grey: no stretch, colour ramp or "
                                                                 "statistics (needs --hillshade)"),
+    band: Optional[int] = typer.Option(None, "--band", help="Render stored band B (1-based) instead of band 1: the "
+                                                            "stretch and the file statistics are that band's"),
+    bands: Optional[str] = typer.Option(None, "--bands", help="A colour composite of three stored bands as 'R,G,B': "
+                                                              "each stretched over its own statistics; --colormap "
+                                                              "stays gray (gamma and transfer shape the curves), no "
+                                                              "--hillshade, --channels 4"),
 ):
     """Render a window of a streaming file as a stretched 8-bit colour image on the GPU (extension)"""
     from . import render as rn
@@ -616,6 +692,24 @@ def render(
         rn.parse_stretch(stretch)
     except ValueError as e:
         fail(str(e))
+    band_kw = {}
+    if band is not None and bands is not None:
+        fail("give --band or --bands, not both")
+    if band is not None:
+        if band < 1:
+            fail(f"--band numbers start at 1, got {band}")
+        band_kw["band"] = band
+    if bands is not None:
+        parts = [p.strip() for p in bands.split(",")]
+        if len(parts) != 3 or not all(p.isascii() and p.isdigit() and int(p) >= 1 for p in parts):
+            fail(f"--bands takes three band numbers 'R,G,B', got {bands!r}")
+        if hillshade is not None:
+            fail("--bands cannot be combined with --hillshade")
+        if channels != 4:
+            fail("--bands writes R, G, B, A: --channels must stay 4")
+        if colormap != "gray":
+            fail("--bands keeps --colormap gray: --gamma and --transfer shape the three curves")
+        band_kw["bands"] = tuple(int(p) for p in parts)
     shade_kw = {}
     if hillshade is None:
         for name, v in (("--z-factor", z_factor), ("--shade-strength", shade_strength),
@@ -669,7 +763,7 @@ def render(
             size = rn.max_size_shape(coords[2] - coords[0], coords[3] - coords[1], max_size)
         img, tr = streaming.render_window(flac_url, coords, size[0], size[1], stretch=stretch, stats_from=stats_from,
                                           colormap=ramp, gamma=gamma, transfer=transfer, resampling=resampling,
-                                          level=level, nodata=nd, channels=channels, **shade_kw)
+                                          level=level, nodata=nd, channels=channels, **shade_kw, **band_kw)
         if suffix == ".png":
             from .png import write_png
             write_png(output, img)
@@ -683,6 +777,10 @@ def render(
             az, alt = shade_kw["hillshade"]
             what = (f"shade only, {resampling}" if shade_only else what) + f", hillshade {az:g},{alt:g}"
             what += f" z-factor {shade_kw.get('z_factor', 1.0):g} strength {shade_kw.get('shade_strength', 1.0):g}"
+        if bands is not None:
+            what += f", bands {bands}"
+        elif band is not None:
+            what += f", band {band}"
         typer.echo(f"SUCCESS: rendered {size[0]}x{size[1]}x{channels} ({what}) -> {output}")
     except (KeyError, LookupError, ValueError) as e:
         typer.echo(f"Error: {e}", err=True)

@@ -193,12 +193,14 @@ def _file_nodata(word, own):
     return float(word)
 
 
-def raster_file_statistics(path, level: int = 0, nodata="file", bins: int = 256, ctx=None) -> Dict:
+def raster_file_statistics(path, level: int = 0, nodata="file", bins: int = 256, ctx=None, band=None) -> Dict:
     """Statistics of a raster file: {"file", "kind", "dtype", "width", "height", "level", "nodata", "bands": [...]} with
     one band_statistics entry per band.  A GeoTIFF gives every band: the bands go up once, more than 8 in groups of 8,
     and the nodata value is the file's GDAL_NODATA tag.  A streaming .flac gives the raster of overview level `level`
     through reconstruct_device -- decoded into device memory and never downloaded -- and the nodata value is the
-    index's.  `nodata`: "file" (the default), None / "none" to read without one, or a number that overrides it."""
+    index's.  `nodata`: "file" (the default), None / "none" to read without one, or a number that overrides it.
+    A streaming file of several bands gives every stored band, one reconstruction at a time.  `band` (1-based) selects
+    one band of either kind of file; "band_numbers" names the bands the entries of "bands" describe."""
     from . import geotiff, streaming
     from ._native import default_context
     p = Path(path)
@@ -212,7 +214,13 @@ def raster_file_statistics(path, level: int = 0, nodata="file", bins: int = 256,
         nd = _file_nodata(nodata, r.nodata)
         if nd is not None:
             nd = streaming.nodata_for_dtype(nd, dtype)
-        data = np.ascontiguousarray(r.data if r.data.ndim == 3 else r.data[None])
+        data = r.data if r.data.ndim == 3 else r.data[None]
+        numbers = list(range(1, data.shape[0] + 1))
+        if band is not None:
+            if not 1 <= int(band) <= data.shape[0]:
+                raise LookupError(f"band {band} not in this file (bands present: {numbers})")
+            data, numbers = data[int(band) - 1:int(band)], [int(band)]
+        data = np.ascontiguousarray(data)
         bands: List[Dict] = []
         ctx = ctx or default_context()
         buf = ctx.alloc(data.nbytes)
@@ -231,22 +239,25 @@ def raster_file_statistics(path, level: int = 0, nodata="file", bins: int = 256,
         if level not in streaming.overview_levels(index):
             raise LookupError(f"level {level} is not in the file (levels: {streaming.overview_levels(index)})")
         ctx = ctx or default_context()
-        dst, dtype, li = streaming.reconstruct_device(p, ctx, level)
-        dtype = np.dtype(dtype)
-        try:
-            nd = _file_nodata(nodata, streaming.index_nodata(index))
-            if nd is not None:
-                nd = streaming.nodata_for_dtype(nd, dtype)
-            height, width = int(li["height"]), int(li["width"])
-            d = ctx.make_raster_desc(height, width, dtype)
-            bands = _device_statistics(ctx, dst.ptr, d, nd, int(bins))
-        finally:
-            dst.close()
+        numbers = streaming.bands_of(index) if band is None else [int(band)]
+        bands = []
+        for b in numbers:  # one band in device memory at a time
+            dst, dtype, li = streaming.reconstruct_device(p, ctx, level, bands=None if b == 1 else [b])
+            dtype = np.dtype(dtype)
+            try:
+                nd = _file_nodata(nodata, streaming.index_nodata(index))
+                if nd is not None:
+                    nd = streaming.nodata_for_dtype(nd, dtype)
+                height, width = int(li["height"]), int(li["width"])
+                d = ctx.make_raster_desc(height, width, dtype)
+                bands += _device_statistics(ctx, dst.ptr, d, nd, int(bins))
+            finally:
+                dst.close()
         kind = "streaming"
     else:
         raise ValueError(f"Unsupported file format: {suffix}")
     return {"file": str(path), "kind": kind, "dtype": str(dtype), "width": width, "height": height, "level": level,
-            "nodata": nd, "bands": bands}
+            "nodata": nd, "bands": bands, "band_numbers": numbers}
 
 
 def with_percentiles(band: Dict, qs: Sequence) -> Dict:

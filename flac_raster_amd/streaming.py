@@ -33,6 +33,20 @@ Statistics (extension, ``create_streaming*(stats=True)``): the index gains a top
 level-0 band's valid / nodata / NaN counts, min, max, mean, std and a histogram of at most 256 bins
 (``stats.band_statistics``; non-finite numbers as the same JSON strings), masked by the nodata value in force.  The
 frames and every other key are what they are without it; ``index_statistics`` reads the key back.
+
+Bands (extension, ``create_streaming*(bands=...)``): every selected band of the source is stored as mono tiles of its
+own, band after band -- ``[u32 index length][index][band 1: level-0 tiles, overview tiles][next band: level-0 tiles,
+overview tiles]...`` -- frame ids and byte offsets running on through the file.  Band 1 must be among them: every key
+above keeps its meaning and describes band 1, so a reader that knows nothing of bands sees a valid single-band file.
+One key follows the others::
+
+    "bands": {"count": <bands in the source>, "entries": [
+        {"band": b, "frames": [...], "overviews": {...}, "statistics": {...}}, ...]}
+
+with one entry per stored band other than 1, in file order; ``overviews`` and ``statistics`` are present exactly when
+the top-level ones are, and one ``nodata`` value serves every band.  ``bands_of`` lists the stored bands and
+``band_index`` turns one into a dict of the index's own shape; the readers take ``bands=`` and fetch the named bands'
+tiles only.  Without ``bands`` the file written and the path taken are what they always were.
 """
 from __future__ import annotations
 
@@ -157,6 +171,89 @@ def level_index(index: Dict, level: int = 0) -> Dict:
                 li["nodata"] = index["nodata"]
             return li
     raise LookupError(f"level {level} not in this file (levels present: {overview_levels(index)})")
+
+
+def bands_of(index: Dict) -> List[int]:
+    """The band numbers (1-based, the source's) a streaming index holds, in file order: [1] for a file without a
+    "bands" key.  Pure."""
+    return [1] + [int(e["band"]) for e in (index.get("bands") or {}).get("entries", [])]
+
+
+def band_index(index: Dict, band: int = 1) -> Dict:
+    """A dict of the streaming index's own shape (crs, transform, width, height, tile_size, frames, and nodata /
+    overviews / statistics where the file has them) for one stored band; band 1 is the index without its "bands" key.
+    level_index, window_request, select_frame, intersecting, pick_level and index_statistics work on the result
+    unchanged.  LookupError (naming the bands present) for a band the file does not hold.  Pure."""
+    band = int(band)
+    if band == 1:
+        return {k: v for k, v in index.items() if k != "bands"} if "bands" in index else index
+    for e in (index.get("bands") or {}).get("entries", []):
+        if int(e["band"]) == band:
+            bi = {"crs": index.get("crs"), "transform": list(index["transform"]), "width": index["width"],
+                  "height": index["height"], "tile_size": index.get("tile_size"), "frames": e["frames"]}
+            if "nodata" in index:
+                bi["nodata"] = index["nodata"]
+            for key in ("overviews", "statistics"):
+                if key in e:
+                    bi[key] = e[key]
+            return bi
+    raise LookupError(f"band {band} not in this file (bands present: {bands_of(index)})")
+
+
+def parse_bands(text: str):
+    """A --bands value: "all", or 1-based band numbers separated by commas ("1,2,3") as a list.  ValueError for
+    anything else, a number below 1 and a number given twice.  Pure."""
+    t = str(text).strip().lower()
+    if t == "all":
+        return "all"
+    parts = [p.strip() for p in t.split(",")]
+    if not parts or not all(p.isascii() and p.isdigit() for p in parts):
+        raise ValueError(f"--bands must be 'all' or band numbers separated by commas, got {text!r}")
+    nums = [int(p) for p in parts]
+    if min(nums) < 1:
+        raise ValueError(f"--bands: band numbers start at 1, got {text!r}")
+    if len(set(nums)) != len(nums):
+        raise ValueError(f"--bands: a band is named twice in {text!r}")
+    return nums
+
+
+def select_bands(bands, count: int) -> List[int]:
+    """The bands create_streaming*(bands=...) stores of a source with `count` bands: "all" is 1 .. count, a sequence is
+    checked (whole numbers 1 .. count, none twice) and must name band 1, whose frames the top-level keys of the index
+    describe.  ValueError otherwise.  Pure."""
+    count = int(count)
+    if isinstance(bands, str):
+        bands = parse_bands(bands)
+        if bands == "all":
+            return list(range(1, count + 1))
+    nums = [int(b) for b in bands]
+    if [float(b) for b in bands] != [float(b) for b in nums] or not nums:
+        raise ValueError(f"bands must be whole band numbers, got {list(bands)!r}")
+    if len(set(nums)) != len(nums):
+        raise ValueError(f"a band is named twice in {nums}")
+    bad = [b for b in nums if not 1 <= b <= count]
+    if bad:
+        raise ValueError(f"band {bad[0]} is not one of the source's {count} band(s)")
+    if 1 not in nums:
+        raise ValueError(f"band 1 must be among the stored bands (the index's top-level keys are band 1's), got {nums}")
+    return nums
+
+
+def _bands_to_read(index: Dict, bands) -> List[int]:
+    """The bands a read returns: [1] for None, every stored band for "all", else the named bands, each of which the
+    file must hold (LookupError) and none of which may be named twice."""
+    if bands is None:
+        return [1]
+    if isinstance(bands, str):
+        bands = parse_bands(bands)
+        if bands == "all":
+            return bands_of(index)
+    nums = [int(b) for b in bands]
+    if not nums or len(set(nums)) != len(nums):
+        raise ValueError(f"bands must name at least one band and none twice, got {nums}")
+    for b in nums:
+        band_index(index, b)
+    return nums
 
 
 def pick_level(index: Dict, width_px: int, height_px: int, max_size: int) -> int:
@@ -538,17 +635,136 @@ def create_streaming_array(band: np.ndarray, transform: geotiff.Affine, crs: Opt
     return index
 
 
+def create_streaming_bands_array(bands, band_numbers: Sequence[int], transform: geotiff.Affine, crs: Optional[str],
+                                 output: Path, tile_size: int = 1024, ctx: Optional[Context] = None,
+                                 timings: Optional[Dict[str, float]] = None, overviews: bool = False,
+                                 resampling: str = "average", max_levels: Optional[int] = None, nodata=None,
+                                 stats: bool = False, source_count: Optional[int] = None) -> Dict:
+    """Extension: a streaming file of several bands (module docstring, "Bands").  `bands` is an (N, H, W) array or a
+    sequence of N (H, W) arrays of one shape and dtype; band_numbers[k] is the 1-based number plane k has in its
+    source, and band 1 must be among them (select_bands).  `source_count` (the "count" the index records) defaults to
+    the largest number.  Every band is encoded as mono tiles by the path create_streaming_array takes for band 1 on the
+    device (encode_band_tiles_device), gets overview levels of its own with `overviews` and statistics of its own with
+    `stats`; one `nodata` value serves them all.  The bands go through the device one after the other: the band buffer,
+    the two level buffers and the arena are allocated once, for one band.  Band 1's tiles come first, then the other
+    bands' in the order given.  Returns the index; `timings` gets the stage seconds."""
+    tm = timings if timings is not None else {}
+    planes = [np.asarray(b) for b in bands]
+    count = int(source_count) if source_count is not None else max(int(b) for b in band_numbers)
+    nums = select_bands(list(band_numbers), count)
+    if len(planes) != len(nums):
+        raise ValueError("one band number per plane")
+    H, W = planes[0].shape if planes[0].ndim == 2 else (0, 0)
+    dtype = planes[0].dtype
+    if H == 0 or W == 0 or any(p.shape != (H, W) or p.dtype != dtype for p in planes):
+        raise ValueError("the bands must be non-empty (H, W) arrays of one shape and dtype")
+    if overviews and resampling not in RESAMPLING:
+        raise ValueError(f"resampling must be one of {RESAMPLING}, got {resampling!r}")
+    if nodata is not None:
+        nodata = nodata_for_dtype(nodata, dtype)
+    ctx = ctx or default_context()
+    t0 = time.perf_counter()
+    shapes = [(H, W)] + (overview_shapes(H, W, tile_size, max_levels) if overviews else [])
+    _, bps0 = audio_params(1, min(tile_size, H), dtype)
+    d0 = ctx.make_desc(H, W, dtype, nbands=1, tile_h=tile_size, tile_w=tile_size, sample_rate=44100,
+                       bits_per_sample=bps0)
+    order = [nums.index(1)] + [k for k, b in enumerate(nums) if b != 1]
+    bufs: List = []
+    pyr_s = 0.0
+    encoded = []  # (band number, EncodedTiles per level, statistics or None), in file order
+    try:
+        bufs.append(ctx.alloc(H * W * dtype.itemsize))
+        bufs.append(ctx.alloc(ctx.arena_bound(d0)))
+        band_buf, arena = bufs
+        # level k lives in lv[k % 2], as in _create_streaming_overviews
+        lv = [ctx.alloc(h * w * dtype.itemsize) for h, w in shapes[1:3]]
+        bufs.extend(lv)
+        for k in order:
+            band_buf.upload(planes[k])
+            band_stats = _band_statistics_device(ctx, band_buf.ptr, H, W, dtype, nodata) if stats else None
+            cur, cur_desc = band_buf, ctx.make_raster_desc(H, W, dtype)
+            encs: List[EncodedTiles] = []
+            for level, (h, w) in enumerate(shapes):
+                if level:
+                    tp = time.perf_counter()
+                    nxt = lv[(level - 1) % 2]
+                    cur_desc = ctx.downsample2_device(cur.ptr, cur_desc, nxt.ptr, mode=resampling, nodata=nodata)
+                    cur = nxt
+                    pyr_s += time.perf_counter() - tp
+                encs.append(encode_band_tiles_device(ctx, cur.ptr, h, w, dtype, tile_size, arena,
+                                                     pinned=level == 0 and planes[k].nbytes >= (64 << 20)))
+            encoded.append((nums[k], encs, band_stats))
+    finally:
+        for b in bufs:
+            b.close()
+    t1 = time.perf_counter()
+    tr6 = list(transform)[:6]
+    parts = []  # (headers, enc, body offset) per band and level, in file order
+    fid, total = 0, 0
+    index: Dict = {}
+    entries: List[Dict] = []
+    for num, encs, band_stats in encoded:
+        frames0: List[Dict] = []
+        levels = []
+        for level, ((h, w), enc) in enumerate(zip(shapes, encs)):
+            lt = level_transform(tr6, level)
+            headers, frames, nbytes = streaming_headers(enc, geotiff.Affine(*lt) if level else transform, crs, w, h,
+                                                        tile_size, dtype, frame_id0=fid, byte_offset0=total,
+                                                        nodata=nodata)
+            parts.append((headers, enc, total))
+            fid += len(frames)
+            total += nbytes
+            if level == 0:
+                frames0 = frames
+            else:
+                levels.append({"level": level, "factor": 2 ** level, "width": w, "height": h, "transform": lt,
+                               "frames": frames})
+        if num == 1:  # the keys a single-band file has, in its order
+            entry = index
+            index.update({"crs": str(crs), "transform": list(transform), "width": W, "height": H,
+                          "tile_size": tile_size, "frames": frames0})
+            if nodata is not None:
+                index["nodata"] = _nodata_to_index(nodata)
+        else:
+            entry = {"band": num, "frames": frames0}
+            entries.append(entry)
+        if overviews:
+            entry["overviews"] = {"resampling": resampling, "levels": levels}
+            if nodata is not None:
+                entry["overviews"]["nodata_aware"] = True
+        if band_stats is not None:
+            entry["statistics"] = band_stats
+    index["bands"] = {"count": count, "entries": entries}
+    head = streaming_head(index)
+    t2 = time.perf_counter()
+    fd = os.open(output, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    try:
+        os.ftruncate(fd, len(head) + total)
+        t2b = time.perf_counter()
+        os.pwrite(fd, head, 0)
+        for headers, enc, start in parts:
+            write_tiles(fd, len(head) + start, headers, enc)
+    finally:
+        os.close(fd)
+    t3 = time.perf_counter()
+    tm.update(encode_s=t1 - t0, pyramid_s=pyr_s, index_s=t2 - t1, write_s=t3 - t2, open_truncate_s=t2b - t2,
+              total_s=t3 - t0)
+    return index
+
+
 def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
                      ctx: Optional[Context] = None, timings: Optional[Dict[str, float]] = None,
                      materialize: bool = False, overviews: bool = False, resampling: str = "average",
-                     max_levels: Optional[int] = None, nodata=None, stats: bool = False) -> Dict:
+                     max_levels: Optional[int] = None, nodata=None, stats: bool = False, bands=None) -> Dict:
     """cli.py:620-804 without the console output: writes the streaming file, returns the index.  Band 1 only
     (cli.py:698-699): an uncompressed band-sequential (or single-band) file is encoded straight from its memory map
     (no host copy of the band); otherwise its strips / tiles are decoded.  `timings` gets read_s + the stages of
     create_streaming_array.  materialize=True reads the band into host memory first (read_s is then the whole read;
     otherwise the band's pages are read while the encode copies them, inside encode_s).  overviews / resampling /
     max_levels / nodata / stats: as create_streaming_array; nodata="source" takes the GeoTIFF's GDAL_NODATA tag (ValueError
-    when the file has none)."""
+    when the file has none).  `bands` (extension): "all" or 1-based band numbers, band 1 among them (select_bands):
+    those bands are stored one after the other (create_streaming_bands_array); without it the file and the path taken
+    are what they always were."""
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
     with geotiff.TiffFile(input_file) as tf:
@@ -560,6 +776,18 @@ def create_streaming(input_file: Path, output_file: Path, tile_size: int = 1024,
                 raise ValueError(f"{input_file} has no GDAL_NODATA tag")
             nodata = src_nodata
         crs = f"EPSG:{epsg}" if epsg else None
+        if bands is not None:
+            nums = select_bands(bands, tf.count)
+            planes = [None if materialize else tf.band_view(b - 1) for b in nums]
+            planes = [tf.read_rows(bands=[b - 1])[0] if p is None else p for b, p in zip(nums, planes)]
+            tm["read_s"] = time.perf_counter() - t0
+            transform = transform or geotiff.Affine(1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+            index = create_streaming_bands_array(planes, nums, transform, crs, output_file, tile_size, ctx, tm,
+                                                 overviews=overviews, resampling=resampling, max_levels=max_levels,
+                                                 nodata=nodata, stats=stats, source_count=tf.count)
+            del planes
+            tm["total_s"] = time.perf_counter() - t0
+            return index
         band = None if materialize else tf.band_view(0)
         if band is None:
             band = tf.read_rows(bands=[0])[0]
@@ -771,13 +999,15 @@ def fetch_tiles(src: Union[str, Path, Source], frames: Sequence[Dict], index_siz
 
 def extract_streaming(flac_url: Union[str, Path], output: Path, bbox: Optional[Sequence[float]] = None,
                       tile_id: Optional[int] = None, center: bool = False, last: bool = False,
-                      ctx: Optional[Context] = None, level: int = 0, nodata="index") -> Dict:
+                      ctx: Optional[Context] = None, level: int = 0, nodata="index", band: int = 1) -> Dict:
     """cli.py:875-1039: pick one tile, range-read it, decode it and write it as a GeoTIFF.  `level` (extension):
     pick among the tiles of that overview level (tile ids are the level's own frame ids); the GeoTIFF carries the
-    level tile's transform.  `nodata` (nodata_in_force): the GeoTIFF's nodata tag is the value in force."""
+    level tile's transform.  `nodata` (nodata_in_force): the GeoTIFF's nodata tag is the value in force.  `band`
+    (extension): pick among that stored band's tiles (its frame ids are the ones its index entries carry)."""
     src = Source(flac_url)
     n, index = read_index(src)
-    f = select_frame(level_index(index, level), tile_id=tile_id, last=last, center=center, bbox=bbox)
+    f = select_frame(level_index(band_index(index, band), level), tile_id=tile_id, last=last, center=center,
+                     bbox=bbox)
     data = fetch_tiles(src, [f], n)[0]
     (arr, md), = TileDecoder(ctx).decode_streams([data])
     if not (isinstance(nodata, str) and nodata == "index" and "nodata" not in index):  # else: the tile's own tag
@@ -815,14 +1045,21 @@ def tile_windows(frames: Sequence[Dict], origin: Tuple[int, int] = (0, 0)) -> Li
 
 
 def decode_into_window(streams: Sequence[bytes], frames: Sequence[Dict], origin: Tuple[int, int],
-                       shape: Tuple[int, int], ctx: Optional[Context] = None):
+                       shape: Tuple[int, int], ctx: Optional[Context] = None, dst=None, plane: int = 0,
+                       planes: int = 1):
     """Decode whole tile streams (one per index entry of `frames`) straight into the (height, width) = shape window
     whose upper-left pixel is the raster's (col, row) = origin: one batched decode + placement on the device
     (frs_decode_tiles_window_device), tiles clipped to the window.  Each tile's frame bytes are uploaded to their
     place in the device blob (the body is never concatenated on the host).  Window pixels no tile covers are zero.
-    Returns (DeviceBuffer holding the (1, height, width) raster, its dtype)."""
+    Returns (DeviceBuffer holding the (1, height, width) raster, its dtype).
+    Several bands: the destination is band-planar (planes, height, width) and one call fills plane `plane` of it.
+    Without `dst` the buffer is allocated for `planes` planes; with `dst` (the buffer an earlier call returned) the
+    tiles go into that buffer, which must hold plane `plane` of this dtype."""
     ctx = ctx or default_context()
     h, w = int(shape[0]), int(shape[1])
+    plane, planes = int(plane), int(planes)
+    if plane < 0 or (dst is None and plane >= planes):
+        raise ValueError("plane must be one of the destination's planes")
     metas = [container.parse_metadata(s) for s in streams]
     mds = [container.read_raster_tags(m) for m in metas]
     wins = tile_windows(frames, origin)
@@ -846,33 +1083,59 @@ def decode_into_window(streams: Sequence[bytes], frames: Sequence[Dict], origin:
     sizes = [len(streams[i]) - metas[i].audio_offset for i in order]
     off = np.zeros(len(order) + 1, dtype=np.int64)
     off[1:] = np.cumsum(sizes)
+    pbytes = h * w * dtype.itemsize  # one plane
+    if dst is not None and dst.nbytes < (plane + 1) * pbytes:
+        raise ValueError("the destination buffer does not hold that plane")
     blob = ctx.alloc(int(off[-1]) + 16)
-    dst = ctx.alloc(h * w * dtype.itemsize)
+    own = dst is None
     try:
+        if own:
+            dst = ctx.alloc(planes * pbytes)
         for k, i in enumerate(order):
             blob.upload(np.frombuffer(streams[i], dtype=np.uint8)[metas[i].audio_offset:], int(off[k]))
         # tiles that do not overlap cover the window exactly when their clipped areas add up to it: only then is the
         # zero fill (np.zeros in the host mosaic this replaces) skipped
         covered = sum(max(0, min(w, c + tw) - max(0, c)) * max(0, min(h, r + th) - max(0, r)) for c, r, tw, th in wins)
         if covered != h * w:
-            dst.upload(np.zeros((h, w), dtype=dtype))
+            dst.upload(np.zeros((h, w), dtype=dtype), plane * pbytes)
         k0 = 0
         for (bps, bs), idx in groups.items():
             k1 = k0 + len(idx)
             ctx.decode_tiles_window_device(blob, off[k0:k1 + 1], [wins[i] for i in idx], bps,
                                            [mds[i]["data_min"] for i in idx], [mds[i]["data_max"] for i in idx],
-                                           dtype, dst, (1, h, w), blocksize=bs)
+                                           dtype, dst, (1, h, w), blocksize=bs, dst_ptr=dst.ptr + plane * pbytes)
             k0 = k1
     except BaseException:
-        dst.close()
+        if own and dst is not None:
+            dst.close()
         raise
     finally:
         blob.close()
     return dst, dtype
 
 
-def _download_raster(dst, dtype, h: int, w: int) -> np.ndarray:
-    out = np.empty((1, h, w), dtype=dtype)
+def _decode_bands_into_window(src, index_size: int, band_frames: Sequence[Sequence[Dict]], origin: Tuple[int, int],
+                              shape: Tuple[int, int], ctx: Optional[Context] = None):
+    """decode_into_window for several bands: band_frames[k] holds the index entries of the tiles of plane k.  Only those
+    tiles are fetched; each band's are decoded straight into its plane of one band-planar device buffer.  Returns
+    (DeviceBuffer holding the (len(band_frames), height, width) raster, its dtype)."""
+    dst, dtype = None, None
+    try:
+        for k, frames in enumerate(band_frames):
+            datas = fetch_tiles(src, frames, index_size)
+            dst, dt = decode_into_window(datas, frames, origin, shape, ctx, dst=dst, plane=k, planes=len(band_frames))
+            if dtype is not None and dt != dtype:
+                raise ValueError("the bands of one file share a dtype")
+            dtype = dt
+    except BaseException:
+        if dst is not None:
+            dst.close()
+        raise
+    return dst, dtype
+
+
+def _download_raster(dst, dtype, h: int, w: int, nb: int = 1) -> np.ndarray:
+    out = np.empty((nb, h, w), dtype=dtype)
     try:
         dst.download(out=out)
     finally:
@@ -881,19 +1144,21 @@ def _download_raster(dst, dtype, h: int, w: int) -> np.ndarray:
 
 
 def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: Optional[Context] = None,
-                        crop: bool = True, level: int = 0):
+                        crop: bool = True, level: int = 0, bands=None):
     """Extension: decode every tile intersecting bbox in one GPU batch straight into the raster window
     they cover, or (crop=True) into the whole-pixel window of the bbox itself (bbox_pixel_window): the tiles are
     placed and clipped on the device (decode_into_window), the host only receives the final window.  Returns
     (array (1, h, w), window dict, transform list); with `level` > 0 the tiles, the window and the transform are that
-    overview level's."""
+    overview level's.  `bands` (stored band numbers, or "all"): those bands, (len(bands), h, w); only their tiles
+    are fetched."""
     src = Source(flac_url)
     n, index = read_index(src)
-    index = level_index(index, level)
-    hits = intersecting(index, bbox)
+    sel = _bands_to_read(index, bands)
+    band_hits = [intersecting(level_index(band_index(index, b), level), bbox) for b in sel]
+    index = level_index(band_index(index, sel[0]), level)
+    hits = band_hits[0]
     if not hits:
         raise LookupError(f"No tiles intersect with bbox {bbox}")
-    datas = fetch_tiles(src, hits, n)
     c0 = min(f["window"]["col_off"] for f in hits)
     r0 = min(f["window"]["row_off"] for f in hits)
     c1 = max(f["window"]["col_off"] + f["window"]["width"] for f in hits)
@@ -908,12 +1173,12 @@ def extract_bbox_mosaic(flac_url: Union[str, Path], bbox: Sequence[float], ctx: 
         b1 = min(cw["row_off"] + cw["height"], r1)
         win = {"col_off": a0, "row_off": b0, "width": max(a1 - a0, 0), "height": max(b1 - b0, 0)}
     if win["width"] == 0 or win["height"] == 0:  # an empty pixel window: nothing to decode
-        md = container.read_raster_tags(container.parse_metadata(datas[0]))
-        out = np.zeros((1, win["height"], win["width"]), dtype=np.dtype(md["dtype"]))
+        md = container.read_raster_tags(container.parse_metadata(fetch_tiles(src, hits[:1], n)[0]))
+        out = np.zeros((len(sel), win["height"], win["width"]), dtype=np.dtype(md["dtype"]))
     else:
-        dst, dtype = decode_into_window(datas, hits, (win["col_off"], win["row_off"]), (win["height"], win["width"]),
-                                        ctx)
-        out = _download_raster(dst, dtype, win["height"], win["width"])
+        dst, dtype = _decode_bands_into_window(src, n, band_hits, (win["col_off"], win["row_off"]),
+                                               (win["height"], win["width"]), ctx)
+        out = _download_raster(dst, dtype, win["height"], win["width"], len(sel))
     wt = geotiff.window_transform(t, win["col_off"], win["row_off"])
     return out, win, list(wt)
 
@@ -1025,7 +1290,7 @@ def _fill_in_dtype(fill: float, dtype: np.dtype):
 
 def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, out_h: int,
                 resampling: str = "average", level: Optional[int] = None, fill=None, ctx: Optional[Context] = None,
-                nodata="index"):
+                nodata="index", bands=None):
     """Extension: bbox = [xmin, ymin, xmax, ymax] of band 1 as exactly out_w x out_h pixels.  window_request picks the
     overview level and the tiles; they are range-read (fetch_tiles), decoded and placed into the level's pixel window
     on the device (decode_into_window), resampled there onto the requested grid (frs_resample_window_device, the
@@ -1035,7 +1300,9 @@ def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, o
     turns masking off; with a value in force the masked kernel runs (frs_resample_window_nodata_device): nodata pixels
     stay out of every output, and an output with no valid weight gets `fill`.  `fill` defaults to the nodata value in
     force, else to 0; it must be finite, or NaN for a float raster read with a nodata value.  A file without the key
-    reads exactly as before.  Returns (array (1, out_h, out_w), transform list)."""
+    reads exactly as before.  Returns (array (1, out_h, out_w), transform list).
+    `bands` (a sequence of stored band numbers, or "all"): those bands in that order, (len(bands), out_h, out_w).  Only
+    their tiles are fetched; they are decoded into one band-planar device window and resampled in one call."""
     if resampling not in RESAMPLING_READ:
         raise ValueError(f"resampling must be one of {', '.join(RESAMPLING_READ)}; got {resampling!r}")
     if fill is not None and math.isinf(float(fill)):
@@ -1048,7 +1315,10 @@ def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, o
     fill = float(fill)
     if not (math.isfinite(fill) or (nd is not None and math.isnan(fill))):
         raise ValueError("fill must be finite (or NaN for a float raster read with a nodata value)")
-    req = window_request(index, bbox, out_w, out_h, level)
+    sel = _bands_to_read(index, bands)
+    nb = len(sel)
+    reqs = [window_request(band_index(index, b), bbox, out_w, out_h, level) for b in sel]
+    req = reqs[0]
     out_w, out_h = req["out_w"], req["out_h"]
     if not req["frames"]:
         dtype = _index_dtype(src, index, n)
@@ -1056,31 +1326,31 @@ def read_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int, o
             nodata_for_dtype(nd, dtype)
         if math.isnan(fill) and dtype.kind != "f":
             raise ValueError("a NaN fill needs a float raster")
-        out = np.empty((1, out_h, out_w), dtype=dtype)
+        out = np.empty((nb, out_h, out_w), dtype=dtype)
         out[...] = _fill_in_dtype(fill, dtype)  # the kernel's rule
         return out, req["transform"]
     ctx = ctx or default_context()
     win = req["window"]
-    datas = fetch_tiles(src, req["frames"], n)
-    wdev, dtype = decode_into_window(datas, req["frames"], (win["col_off"], win["row_off"]),
-                                     (win["height"], win["width"]), ctx)
+    wdev, dtype = _decode_bands_into_window(src, n, [r["frames"] for r in reqs], (win["col_off"], win["row_off"]),
+                                            (win["height"], win["width"]), ctx)
     try:
-        dst = ctx.alloc(out_h * out_w * dtype.itemsize)
+        dst = ctx.alloc(nb * out_h * out_w * dtype.itemsize)
     except BaseException:
         wdev.close()
         raise
     try:
         if nd is not None:
             nodata_for_dtype(nd, dtype)
-        ctx.resample_window_device(wdev.ptr, ctx.make_raster_desc(win["height"], win["width"], dtype), dst.ptr,
-                                   ctx.make_raster_desc(out_h, out_w, dtype), req["rect"], resampling, fill,
-                                   nodata=nd)
+        # every plane in one call
+        ctx.resample_window_device(wdev.ptr, ctx.make_raster_desc(win["height"], win["width"], dtype, nbands=nb),
+                                   dst.ptr, ctx.make_raster_desc(out_h, out_w, dtype, nbands=nb), req["rect"],
+                                   resampling, fill, nodata=nd)
     except BaseException:
         dst.close()
         raise
     finally:
         wdev.close()
-    return _download_raster(dst, dtype, out_h, out_w), req["transform"]
+    return _download_raster(dst, dtype, out_h, out_w, nb), req["transform"]
 
 
 STATS_FROM = ("auto", "file", "window")
@@ -1108,8 +1378,16 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
                   transfer: str = "linear", lut_size: Optional[int] = None, resampling: str = "average",
                   level: Optional[int] = None, nodata="index", channels: int = 4, nodata_rgba=(0, 0, 0, 0),
                   ctx: Optional[Context] = None, hillshade: Optional[Sequence[float]] = None, z_factor: float = 1.0,
-                  shade_strength: float = 1.0, shade_only: bool = False):
+                  shade_strength: float = 1.0, shade_only: bool = False, band: int = 1, bands=None):
     """Extension: bbox = [xmin, ymin, xmax, ymax] of band 1 as a stretched 8-bit image of exactly out_w x out_h pixels.
+    `band` renders another stored band by the same path: the stretch and the file statistics are that band's
+    (band_index).  `bands` = (r, g, b) renders a colour composite of three stored bands instead
+    (frs_render_composite_window_device): their tiles alone are fetched and decoded into one band-planar device window,
+    and one kernel resamples the three planes, stretches each over its own limits -- each band's stored statistics
+    under stats_from "file" / "auto", each plane of the decoded window under "window"; range:lo,hi applies to all
+    three -- and writes R, G, B, A.  A pixel where any of the three bands has no data takes nodata_rgba.  The colormap
+    must stay "gray": gamma and transfer shape the three (equal) curves.  hillshade and channels other than 4 are
+    rejected with `bands`.
     With hillshade = (azimuth, altitude) in degrees the image is shaded by frs_render_shaded_window_device: Horn's
     gradient on the output grid, the output pixel's ground size (xmax - xmin) / out_w by (ymax - ymin) / out_h, heights
     multiplied by z_factor, the colours scaled by render.shade_table(shade_strength).  The decoded window then reaches
@@ -1144,6 +1422,18 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
     channels = int(channels)
     if channels not in (1, 2, 4):
         raise ValueError(f"channels must be 1, 2 or 4; got {channels}")
+    if bands is not None:
+        bands = [int(b) for b in bands]
+        if len(bands) != 3:
+            raise ValueError(f"a composite takes three bands (r, g, b); got {bands}")
+        if int(band) != 1:
+            raise ValueError("give band or bands, not both")
+        if hillshade is not None:
+            raise ValueError("a composite cannot be hillshaded")
+        if channels != 4:
+            raise ValueError("a composite is written with 4 channels (R, G, B, A)")
+        if not (isinstance(colormap, str) and colormap == "gray"):
+            raise ValueError('a composite keeps the "gray" colormap: gamma and transfer shape its curves')
     shade = None
     if hillshade is None:
         if shade_only or z_factor != 1.0 or shade_strength != 1.0:
@@ -1166,6 +1456,10 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
     src = Source(flac_url)
     n, index = read_index(src)
     nd = nodata_in_force(index, nodata)
+    if bands is not None:
+        return _render_composite(src, n, index, bands, bbox, out_w, out_h, stretch, kind, stats_from, lut, packed,
+                                 resampling, level, nd, ctx)
+    index = band_index(index, band)
     file_stats = None
     if kind != "range" and stats_from != "window":
         try:
@@ -1216,32 +1510,93 @@ def render_window(flac_url: Union[str, Path], bbox: Sequence[float], out_w: int,
     return out, req["transform"]
 
 
-def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0):
+def _render_composite(src: "Source", n: int, index: Dict, bands: Sequence[int], bbox, out_w: int, out_h: int,
+                      stretch: str, kind: str, stats_from: str, lut, packed: int, resampling: str,
+                      level: Optional[int], nd: Optional[float], ctx: Optional[Context]):
+    """render_window(bands=(r, g, b)) behind its argument checks: (uint8 (out_h, out_w, 4), transform list)."""
+    from . import render as rn
+    bis = [band_index(index, b) for b in bands]
+    file_stats: List[Optional[Dict]] = [None, None, None]
+    if kind != "range" and stats_from != "window":
+        for k, bi in enumerate(bis):
+            try:
+                file_stats[k] = _file_statistics_for(bi, nd)
+            except (LookupError, ValueError):
+                if stats_from == "file":
+                    raise
+    reqs = [window_request(bi, bbox, out_w, out_h, level) for bi in bis]
+    req = reqs[0]
+    out_w, out_h = req["out_w"], req["out_h"]
+    if not req["frames"]:
+        out = np.empty((out_h, out_w, 4), dtype=np.uint8)
+        out[...] = [packed & 0xFF, (packed >> 8) & 0xFF, (packed >> 16) & 0xFF, packed >> 24]
+        return out, req["transform"]
+    ctx = ctx or default_context()
+    win = req["window"]
+    wdev, dtype = _decode_bands_into_window(src, n, [r["frames"] for r in reqs], (win["col_off"], win["row_off"]),
+                                            (win["height"], win["width"]), ctx)
+    dst = None
+    try:
+        if nd is not None:
+            nd = nodata_for_dtype(nd, dtype)
+        plane = win["height"] * win["width"] * dtype.itemsize
+        sd1 = ctx.make_raster_desc(win["height"], win["width"], dtype)
+        lo3, hi3 = [], []
+        for k in range(3):
+            if kind == "range":
+                stats = None
+            elif file_stats[k] is not None:
+                stats = file_stats[k]
+            else:
+                from .stats import _device_statistics
+                stats = _device_statistics(ctx, wdev.ptr + k * plane, sd1, nd, RENDER_WINDOW_BINS)[0]
+            lo, hi = rn.stretch_limits(stats, stretch)
+            lo3.append(lo)
+            hi3.append(hi)
+        dst = ctx.alloc(out_h * out_w * 4)
+        ctx.render_composite_window_device(wdev.ptr, ctx.make_raster_desc(win["height"], win["width"], dtype, nbands=3),
+                                           dst.ptr, out_h, out_w, req["rect"], resampling, lo3, hi3, lut,
+                                           nodata_rgba=packed, nodata=nd)
+        out = np.empty((out_h, out_w, 4), dtype=np.uint8)
+        dst.download(out=out)
+    finally:
+        wdev.close()
+        if dst is not None:
+            dst.close()
+    return out, req["transform"]
+
+
+def reconstruct_device(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0, bands=None):
     """Every tile of a streaming file (of overview level `level`) in one batched decode, placed into the level's full
-    raster in device memory.  Returns (DeviceBuffer, dtype, level_index(index, level))."""
+    raster in device memory.  Returns (DeviceBuffer, dtype, level_index(index, level)).  `bands` (stored band numbers,
+    or "all"): the buffer is band-planar (len(bands), H, W), one batched decode per band, and the index returned is the
+    first named band's."""
     src = Source(flac_url)
     n, index = read_index(src)
-    index = level_index(index, level)
-    frames = index["frames"]
-    if not frames:
+    sel = _bands_to_read(index, bands)
+    levels = [level_index(band_index(index, b), level) for b in sel]
+    index = levels[0]
+    if not all(li["frames"] for li in levels):
         raise ValueError("the streaming index lists no tiles")
-    datas = fetch_tiles(src, frames, n)
-    dst, dtype = decode_into_window(datas, frames, (0, 0), (int(index["height"]), int(index["width"])), ctx)
+    dst, dtype = _decode_bands_into_window(src, n, [li["frames"] for li in levels], (0, 0),
+                                           (int(index["height"]), int(index["width"])), ctx)
     return dst, dtype, index
 
 
-def reconstruct(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0):
-    """The whole raster of a streaming file, or of one overview level: (array (1, H, W), transform list)."""
-    dst, dtype, index = reconstruct_device(flac_url, ctx, level)
-    return _download_raster(dst, dtype, int(index["height"]), int(index["width"])), list(index["transform"])
+def reconstruct(flac_url: Union[str, Path], ctx: Optional[Context] = None, level: int = 0, bands=None):
+    """The whole raster of a streaming file, or of one overview level: (array (1, H, W), transform list); with `bands`
+    (stored band numbers, or "all") the array is (len(bands), H, W)."""
+    dst, dtype, index = reconstruct_device(flac_url, ctx, level, bands)
+    nb = dst.nbytes // (int(index["height"]) * int(index["width"]) * np.dtype(dtype).itemsize)
+    return _download_raster(dst, dtype, int(index["height"]), int(index["width"]), nb), list(index["transform"])
 
 
 def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context] = None, level: int = 0,
-                nodata="index") -> Dict:
+                nodata="index", bands=None) -> Dict:
     """extract-streaming --all: write the reconstruction (of overview level `level`) as a GeoTIFF with the index's CRS
     and the level's transform, and the nodata value in force (nodata_in_force) as its nodata tag.  Returns
-    level_index(index, level)."""
-    arr, tr = reconstruct(flac_url, ctx, level)
+    level_index(index, level).  `bands` (stored band numbers, or "all"): a GeoTIFF of those bands."""
+    arr, tr = reconstruct(flac_url, ctx, level, bands)
     _, index = read_index(flac_url)
     nd = nodata_in_force(index, nodata)
     index = level_index(index, level)
@@ -1251,7 +1606,8 @@ def extract_all(flac_url: Union[str, Path], output: Path, ctx: Optional[Context]
     return index
 
 
-def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optional[Context] = None) -> Dict:
+def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optional[Context] = None,
+                     band_number: int = 1) -> Dict:
     """create-streaming --verify: read the written file back (what is checked is what is on disk), decode it into a
     device raster through the window call, upload the source band and compare the two on the device
     (frs_compare_device).  Returns the un-wrapped differences as compare's ``exact`` key: n_different,
@@ -1262,11 +1618,13 @@ def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optiona
     level is compared with it.  The result then also holds ``levels_checked`` (level 0 included) and ``levels``, one
     dict per level (``level`` + the four keys above); the four top-level keys describe the first level that differs,
     or level 0 when none does.  Where the index says ``nodata_aware`` the pyramid is recomputed with the masked step
-    and the index's nodata value."""
+    and the index's nodata value.  `band_number`: the stored band that `band` is the source of (its tiles, levels and
+    overview settings are the ones checked)."""
     from .compare import _exact
     ctx = ctx or default_context()
     band = np.asarray(band)
-    dst, dtype, index = reconstruct_device(flac_path, ctx)
+    sel = None if int(band_number) == 1 else [int(band_number)]
+    dst, dtype, index = reconstruct_device(flac_path, ctx, bands=sel)
     bufs = [dst]
     try:
         H, W = int(index["height"]), int(index["width"])
@@ -1295,7 +1653,7 @@ def verify_streaming(flac_path: Union[str, Path], band: np.ndarray, ctx: Optiona
             if cur is not srcbuf:
                 cur.close()
             cur = nxt
-            got, gdt, _ = reconstruct_device(flac_path, ctx, k)
+            got, gdt, _ = reconstruct_device(flac_path, ctx, k, bands=sel)
             bufs.append(got)
             if gdt != dtype:
                 raise ValueError(f"overview level {k} is {gdt}, the file's level 0 is {dtype}")

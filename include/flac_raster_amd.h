@@ -477,6 +477,40 @@ int frs_render_shaded_window(frs_ctx *ctx, const frs_raster_desc *src, const voi
                              const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
                              const double *nodata, const frs_render_params *render, const frs_shade_params *shade);
 
+/* Render a rectangle of THREE bands as one stretched 8-bit colour image: frs_render_window* with a plane per colour
+ * channel, in one pass over the output (the tap indices and weights of an output are computed once and applied to the
+ * three planes).  csrc/frs_composite.h holds the arithmetic for host and device; the definition is this library's own.
+ * The source is band-planar [3][H][W] of any of the seven dtypes (src->nbands == 3, row and band strides in elements,
+ * band_stride >= (H - 1) * row_stride + W); map, mode and nodata (null, or a pointer at the one nodata value of all
+ * three planes) mean what they mean in frs_render_window*.
+ *   v_c, has_data_c   for c in {0, 1, 2}: exactly what frs_render_window* computes for plane c alone: same taps,
+ *                     weights, rounding, nudge and NaN rule.
+ *   quantise          i_c = the index frs_render_window* gives v_c under lo[c], hi[c] and n.
+ *   colour            byte c of the pixel is byte c of lut[i_c]: R from the R bytes of the table, G from its G bytes, B
+ *                     from its B bytes (a grey ramp with gamma is three equal curves; the columns may differ).  A = 255.
+ *                     A pixel where any of the three planes has no data is nodata_rgba, whole.
+ * lut holds n (1 .. 4096) entries of 4 bytes R, G, B, A (a host pointer: the call copies it); nodata_rgba is packed
+ * R | G << 8 | B << 16 | A << 24.  The destination is pixel-interleaved uint8 [height][width][4] (R, G, B, A; no other
+ * channel count): dst->dtype FRS_DT_U8, dst->width in pixels, dst->row_stride in BYTES (>= width * 4), dst->nbands 1.
+ * No byte outside [height][width * 4] of any row is written (whole 16-byte chunks of a destination row by aligned
+ * 16-byte stores, the rest byte by byte); nothing is read outside any plane's [H][W].  FRS_E_ARG, before anything is
+ * sized, copied or launched: everything frs_render_window* rejects (with C = 4, and each lo[c], hi[c] pair checked like
+ * its lo, hi), except that src->nbands must be 3; a band stride smaller than the plane's extent; null parameters; and a
+ * destination that overlaps any of the three planes.  Synchronous on the context stream; profile entry
+ * "render_composite".  frs_render_composite_window takes host rasters, staged like frs_render_window's. */
+typedef struct {
+    double lo[3], hi[3];
+    const uint8_t *lut; /* host: n * 4 bytes */
+    int32_t n;
+    uint32_t nodata_rgba;
+} frs_composite_params;
+int frs_render_composite_window_device(frs_ctx *ctx, const frs_raster_desc *src, const void *src_dev,
+                                       const frs_raster_desc *dst, void *dst_dev, const frs_window_map *map,
+                                       int32_t mode, const double *nodata, const frs_composite_params *composite);
+int frs_render_composite_window(frs_ctx *ctx, const frs_raster_desc *src, const void *src_host,
+                                const frs_raster_desc *dst, void *dst_host, const frs_window_map *map, int32_t mode,
+                                const double *nodata, const frs_composite_params *composite);
+
 /* Multi-GPU create-streaming (one process per GPU).  The reference's tile loop (cli.py:690-763) is
  * serial; here tiles shard by contiguous tile rows and the only exchange is an RCCL all-gather (xGMI) of per-tile
  * byte sizes, after which every rank writes its own tiles at their file offsets.  librccl.so is loaded at run
@@ -516,7 +550,8 @@ int frs_synth_raster_device(frs_ctx *ctx, int16_t *dev, int32_t bands, int64_t h
 void *frs_ctx_stream(frs_ctx *ctx);
 /* Average device time (ms) of the named kernel over the launches since the last reset, measured with
  * HIP events on the context stream (kernel: "encode" = the frame-encode kernel, "analyze", "stats",
- * "compact", "decode", "compare", "place", "pyramid", "resample", "band_stats", "band_hist"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
+ * "compact", "decode", "compare", "place", "pyramid", "resample", "band_stats", "band_hist", "render",
+ * "render_shaded", "render_composite"); returns -1 when not recorded.  frs_profile_enable(ctx, 1) turns recording on. */
 int frs_profile_enable(frs_ctx *ctx, int on);
 double frs_profile_avg_ms(frs_ctx *ctx, const char *kernel);
 void frs_profile_reset(frs_ctx *ctx);
