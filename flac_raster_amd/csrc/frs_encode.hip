@@ -260,6 +260,9 @@ template <int DT> __device__ inline void tile_norm_finalize(TileNorm &n, int nor
     if constexpr (Elem<DT>::is_float) {
         n.dmin = key2f(n.imin);
         n.dmax = key2f(n.imax);
+        // np.min / np.max propagate NaN.  A NaN's key lies beyond +-inf's, so one in the tile arrives as imax (sign
+        // clear) or as imin (sign set): either way both extremes are NaN (converter.py:152-153)
+        if (n.dmin != n.dmin || n.dmax != n.dmax) n.dmin = n.dmax = __builtin_nan("");
         n.den = 0.0;
         n.has_range = n.dmax > n.dmin;
     } else {
@@ -415,8 +418,8 @@ __device__ inline SubAnalysis generic_decide(const double *acc, const uint64_t *
             for (int k = 0; k < 5; k++)
                 fb[k] = (float)(Ts[k] > 0 ? log(M_LN2 * (double)Ts[k] / dn) / M_LN2 : 0.0);
         }
-        // 32-bit streams: constant / fixed decisions come from k_analyze_fixed_wide (limit_residual
-        // estimator); a constant block there clears the LPC candidate again.
+        // 32-bit streams: constant / fixed decisions come from k_analyze_fixed_wide (the limit_residual or the
+        // plain estimator, by the subframe's width); a constant block there clears the LPC candidate again.
         if (!WIDE && fb[1] == 0.0f && diff == 0) {
             A.flags |= kFlagConstant;
         } else {
@@ -961,8 +964,45 @@ __device__ inline void fixed_wide_decide(SubAnalysis &A, const uint64_t *tt, con
     }
 }
 
-// 32-bit streams (bits_per_sample 24 -> pyflac bps 32) use libFLAC's limit_residual fixed estimator;
-// it needs 64-bit errors and validity tracking, done in a separate exact pass per lane.
+// libFLAC 1.4.3 FLAC__fixed_compute_best_predictor(_wide)'s choice from the totals pt of orders 0..4 over samples
+// 4..n-1 of the wasted-bit-shifted signal (the first minimum wins; every estimate comes from its own total), then
+// process_subframe_'s constant test and FIXED estimate test as in fixed_wide_decide.  process_subframe_ takes this
+// estimator for a subframe below 28 bits, whatever the stream's width.
+template <typename IsConstant>
+__device__ inline void fixed_plain_decide(SubAnalysis &A, const uint64_t *pt, int n, int sbps, IsConstant is_constant) {
+    uint64_t m = pt[1] < pt[2] ? pt[1] : pt[2];
+    m = m < pt[3] ? m : pt[3];
+    m = m < pt[4] ? m : pt[4];
+    int order;
+    if (pt[0] <= m) order = 0;
+    else {
+        uint64_t m2 = pt[2] < pt[3] ? pt[2] : pt[3];
+        m2 = m2 < pt[4] ? m2 : pt[4];
+        if (pt[1] <= m2) order = 1;
+        else if (pt[2] <= (pt[3] < pt[4] ? pt[3] : pt[4])) order = 2;
+        else if (pt[3] <= pt[4]) order = 3;
+        else order = 4;
+    }
+    const double dn = (double)(n - 4);
+    auto bits = [&](uint64_t t) { return (float)(t > 0 ? log(M_LN2 * (double)t / dn) / M_LN2 : 0.0); };
+    int flags = A.flags & ~(kFlagConstant | kFlagFixedOk);
+    if (bits(pt[1]) == 0.0f && is_constant()) {
+        A.flags = (flags & ~kFlagLpcOk) | kFlagConstant;
+    } else {
+        A.fixed_order = order;
+        uint64_t tg = pt[0];
+#pragma unroll
+        for (int k = 1; k < 5; k++)
+            if (k == order) tg = pt[k];
+        if (!(bits(tg) >= (float)sbps)) flags |= kFlagFixedOk;
+        A.flags = flags;
+    }
+}
+
+// 32-bit streams (bits_per_sample 24 -> pyflac bps 32): process_subframe_ picks the fixed estimator per subframe from
+// subframe_bps = bps - wasted (+ 1 for a side signal) -- limit_residual at 28 bits and above, the plain one below
+// (every float32 sample of |x| >= 32 carries 5 wasted bits, so a float32 DEM between 32 and 256 is all plain).
+// Both need 64-bit errors, limit_residual validity tracking too; done in a separate exact pass per lane.
 template <int DT, bool ST = false>
 __global__ void __launch_bounds__(128) k_analyze_fixed_wide(const typename Elem<DT>::T *raster, EncodeParams P,
                                                            const TileGeom *tiles, const TileNorm *norms,
@@ -999,7 +1039,8 @@ __global__ void __launch_bounds__(128) k_analyze_fixed_wide(const typename Elem<
         return x;
     };
     int64_t h1 = 0, h2 = 0, h3 = 0, h4 = 0;
-    uint64_t tt[5] = {0, 0, 0, 0, 0};
+    uint64_t tt[5] = {0, 0, 0, 0, 0};  // limit_residual: every sample, an order's first samples excepted
+    uint64_t pt[5] = {0, 0, 0, 0, 0};  // plain: samples 4..n-1
     bool valid[5] = {true, true, true, true, true};
     for (int i = 0; i < n; i++) {
         const int64_t x = next() >> w;
@@ -1017,6 +1058,7 @@ __global__ void __launch_bounds__(128) k_analyze_fixed_wide(const typename Elem<
 #pragma unroll
         for (int k = 0; k < 5; k++) {
             tt[k] += e[k];
+            if (i >= 4) pt[k] += e[k];
             if (e[k] > (uint64_t)INT32_MAX) valid[k] = false;
         }
         h4 = h3;
@@ -1024,7 +1066,7 @@ __global__ void __launch_bounds__(128) k_analyze_fixed_wide(const typename Elem<
         h2 = h1;
         h1 = x;
     }
-    fixed_wide_decide(A, tt, valid, n, sbps, [&]() {
+    auto is_constant = [&]() {
         // all samples equal?  (rare; re-walk)
         row = s0 / g.w;
         col = (int)(s0 - row * g.w);
@@ -1036,7 +1078,9 @@ __global__ void __launch_bounds__(128) k_analyze_fixed_wide(const typename Elem<
             else if (x != first) return false;
         }
         return true;
-    });
+    };
+    if (sbps < 28) fixed_plain_decide(A, pt, n, sbps, is_constant);
+    else fixed_wide_decide(A, tt, valid, n, sbps, is_constant);
     out[sub] = A;
 }
 

@@ -836,11 +836,14 @@ int orc_normalize(const void *src, int dtype, int64_t n, int bits_per_sample, do
     if (dtype == 6 || dtype == 7) {
         /* float data is used as-is (converter.py:61-64), then * 8388607 (bps 24) in the input float type */
         double mn = INFINITY, mx = -INFINITY;
+        int has_nan = 0;
         for (int64_t i = 0; i < n; i++) {
             double v = dtype == 6 ? (double)((const float *)src)[i] : ((const double *)src)[i];
+            if (v != v) has_nan = 1;
             if (v < mn) mn = v;
             if (v > mx) mx = v;
         }
+        if (has_nan) mn = mx = NAN; /* np.min / np.max propagate NaN (converter.py:152-153) */
         *out_min = mn; *out_max = mx;
         for (int64_t i = 0; i < n; i++) {
             if (dtype == 6) {

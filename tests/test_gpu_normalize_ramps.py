@@ -306,7 +306,9 @@ def _wide_rasters():
 @pytest.mark.parametrize("name", list(_wide_rasters()))
 def test_32_bit_scale(gpu_ctx, name):
     """int32, uint32 and float rasters on the generic kernels (the fast paths are 16-bit).  Floats of |x| >= 256 are
-    left out: they give INT32_MIN samples, where libFLAC's own behaviour is not restated."""
+    left out here: they give INT32_MIN samples, which tests/wide_cells.py places frame by frame (NaN, +-inf, 257.0,
+    -300.0) and tests/test_gpu_wide_cells.py compares with the oracle's restatement of libFLAC's limit_residual
+    routines."""
     band, T = _wide_rasters()[name]
     if name.endswith("ramps"):
         assert all(np.unique(t).size == 70001 for t in tiles_of(band, T))
