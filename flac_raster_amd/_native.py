@@ -97,6 +97,18 @@ def stats_groups(items: int, nbands: int, block: int = STATS_BLOCK, unroll: int 
     return max(1, min(-(-items // chunk), max(1, max_groups // nbands)))
 
 
+def encode_align_class(base_ptr: int, es: int, row_stride: int, band_stride: int, tile_w: int, nbands: int) -> int:
+    """Alignment class of the level-5 fast encoders' row segments (mirrors align_class as fast_analyze in
+    csrc/frs_encode.hip uses it): the widest of 16, 8, 4 bytes dividing the address of the first coded band's origin
+    (`base_ptr`), the row stride and the tile width in bytes and, with more than one band, the band stride; 0 (the
+    element gather) when none does.  Strides and tile width in elements of `es` bytes."""
+    strides = [row_stride * es, tile_w * es] + ([band_stride * es] if nbands > 1 else [])
+    for a in (16, 8, 4):
+        if base_ptr % a == 0 and all(s % a == 0 for s in strides):
+            return a
+    return 0
+
+
 class NativeUnavailable(RuntimeError):
     """The HIP library or a gfx950 device is missing (no CPU fallback exists)."""
 

@@ -4434,9 +4434,11 @@ static int fast_analyze(EncodeJob<DT> &J, const void *raster_dev) {
     const bool st2 = J.stereo_fast();
     const int64_t es = (int64_t)sizeof(T);
     // alignment class of the 64-sample row segments (tiles whose width is a multiple of 64): the widest of 16,
-    // 8, 4 bytes dividing the band base, the row stride and the tile width in bytes
+    // 8, 4 bytes dividing the band base, the row stride and the tile width in bytes, and with more than one band
+    // the band stride (the other bands' bases)  (flac_raster_amd/_native.py encode_align_class mirrors this)
     const uintptr_t b0 = reinterpret_cast<uintptr_t>(raster_dev) + (size_t)d->band0 * d->band_stride * es;
-    P.vec_ok = align_class(b0, {16, 8, 4}, {d->row_stride * es, (int64_t)d->tile_w * es});
+    P.vec_ok = align_class(b0, {16, 8, 4},
+                           {d->row_stride * es, d->nbands > 1 ? d->band_stride * es : 0, (int64_t)d->tile_w * es});
     FRS_HIP(ctx->luts.ensure(sizeof(int16_t) * (size_t)kLutCap * ntiles));
     FRS_HIP(ctx->status.ensure(sizeof(uint64_t) * (J.nframes + 1) + 64));
     if (!J.fuse_stats) k_build_lut<DT><<<ntiles, 256, 0, st>>>(J.dnorms, ctx->luts.as<int16_t>());

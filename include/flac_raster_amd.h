@@ -67,7 +67,9 @@ enum frs_status {
  * edge tiles truncated.  Each tile is one FLAC stream whose channels are `nbands` bands starting at
  * band `band0` (create-streaming: nbands = 1, band0 = 0 -- cli.py:699 reads band 1 only; plain convert:
  * one tile covering the raster with nbands = count, converter.py:185-189).  Only the tiles
- * [tile_begin, tile_end) of the row-major tile grid are encoded (multi-GPU sharding). */
+ * [tile_begin, tile_end) of the row-major tile grid are encoded (multi-GPU sharding).
+ * The raster's origin, row_stride and band_stride need element alignment only: a wider common alignment of the band
+ * bases, the row stride and the tile width (16, 8 or 4 bytes) only selects faster loads, never other output. */
 typedef struct {
     int64_t height, width;      /* raster size in pixels */
     int64_t row_stride;         /* elements between rows */
