@@ -33,6 +33,7 @@
 #include "frs_internal.h"
 #include "frs_frame_header.h"
 #include "frs_crc16_fold.h"
+#include "frs_store_select.h"
 
 namespace frs {
 
@@ -2776,14 +2777,18 @@ __device__ __forceinline__ void resolve_and_store(const EncodeParams &P, Pending
             const int fl = has ? __builtin_ctzll(has) : 64;  // lane holding the nearest inclusive
             const int first_i = fl < 64 ? __builtin_amdgcn_readlane(my_first, fl) : kPer;
             // entries at distance <= (fl, first_i) are needed
+            // An aggregate is one frame's size (< 2^14 bytes), so the aggregates add up in 32 bits; only the inclusive
+            // entry (lane fl, entry first_i) is wide, and it is taken by readlane below
             bool missing = false;
-            uint64_t mine = 0;
+            uint32_t mine = 0;
+            uint64_t incl = 0;
 #pragma unroll
             for (int i = 0; i < kPer; i++) {
                 const bool need = lane < fl || (lane == fl && i <= first_i);
                 if (need) {
                     missing |= (sv[i] >> 62) == 0;
-                    mine += sv[i] & kValMask;
+                    if (lane == fl && i == first_i) incl = sv[i] & kValMask;
+                    else mine += (uint32_t)sv[i];
                 }
             }
             if (__ballot(missing)) {  // a needed predecessor has not published yet
@@ -2799,8 +2804,12 @@ __device__ __forceinline__ void resolve_and_store(const EncodeParams &P, Pending
                 __builtin_amdgcn_s_setprio(2);
                 continue;
             }
-            accum += dpp_wave_sum_u64(mine);
-            if (fl < 64) break;
+            accum += dpp_wave_sum_u32(mine);
+            if (fl < 64) {
+                accum += ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(incl >> 32), fl) << 32) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)incl, fl);
+                break;
+            }
             hi -= 64 * kPer;
         }
         prefix = accum;
@@ -2826,37 +2835,34 @@ __device__ __forceinline__ void resolve_and_store(const EncodeParams &P, Pending
         uint4 *d16 = reinterpret_cast<uint4 *>(dst + a0);
         // 16-B chunk ci = words sb + 4 ci .. sb + 4 ci + 4.  Lane L takes the chunks of column L (ci = L C/4 + j),
         // so at each step the 64 lanes read one buffer row: consecutive banks
-        auto chunk = [&](uint32_t ci) {
-            const uint32_t wq = sb + 4 * ci;
-            const uint32_t w0 = __builtin_bswap32(fbuf[M(wq)]), w1 = __builtin_bswap32(fbuf[M(wq + 1)]);
-            const uint32_t w2 = __builtin_bswap32(fbuf[M(wq + 2)]), w3 = __builtin_bswap32(fbuf[M(wq + 3)]);
-            const uint32_t w4 = __builtin_bswap32(fbuf[M(wq + 4)]);
+        // Output word i holds the stream bytes 4 i + r .. 4 i + r + 3: one byte-select (v_perm_b32) on the raw pair
+        // {w[i + 1], w[i]} does the byte swap and the alignment; the selector is wave-uniform (frs_store_select.h)
+        const uint32_t sel = frs::store_select(r);
+        auto out4 = [&](uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
             uint4 o4;
-            o4.x = __builtin_amdgcn_alignbyte(w1, w0, r);
-            o4.y = __builtin_amdgcn_alignbyte(w2, w1, r);
-            o4.z = __builtin_amdgcn_alignbyte(w3, w2, r);
-            o4.w = __builtin_amdgcn_alignbyte(w4, w3, r);
-            d16[ci] = o4;
+            o4.x = __builtin_amdgcn_perm(w1, w0, sel);
+            o4.y = __builtin_amdgcn_perm(w2, w1, sel);
+            o4.z = __builtin_amdgcn_perm(w3, w2, sel);
+            o4.w = __builtin_amdgcn_perm(w4, w3, sel);
+            return o4;
         };
         // the chunks whose first word lies in column L: at each step the lanes read rows within 3 of each
         // other in their own columns, i.e. distinct banks
         const uint32_t c0 = (uint32_t)lane * M.c, c1 = c0 + M.c;
         const uint32_t ci0 = c0 > sb ? (c0 - sb + 3) >> 2 : 0u, ci1 = c1 > sb ? min(n16, (c1 - sb + 3) >> 2) : 0u;
-        // chunks before the column's last lie wholly in column L: rows r .. r + 4 at phys r * 64 + L
+        // chunks before the column's last lie wholly in column L: rows r .. r + 4 at phys r * 64 + L.  A chunk's fifth
+        // word is the next chunk's first (in column L too: every chunk here begins there), carried in a register
         if (ci0 < ci1) {
             const uint32_t *cp = fbuf + M(sb + 4 * ci0);
+            uint32_t w0 = cp[0];
             for (uint32_t ci = ci0; ci + 1 < ci1; ci++, cp += 256) {
-                const uint32_t w0 = __builtin_bswap32(cp[0]), w1 = __builtin_bswap32(cp[64]);
-                const uint32_t w2 = __builtin_bswap32(cp[128]), w3 = __builtin_bswap32(cp[192]);
-                const uint32_t w4 = __builtin_bswap32(cp[256]);
-                uint4 o4;
-                o4.x = __builtin_amdgcn_alignbyte(w1, w0, r);
-                o4.y = __builtin_amdgcn_alignbyte(w2, w1, r);
-                o4.z = __builtin_amdgcn_alignbyte(w3, w2, r);
-                o4.w = __builtin_amdgcn_alignbyte(w4, w3, r);
-                d16[ci] = o4;
+                const uint32_t w1 = cp[64], w2 = cp[128], w3 = cp[192], w4 = cp[256];
+                d16[ci] = out4(w0, w1, w2, w3, w4);
+                w0 = w4;
             }
-            chunk(ci1 - 1);
+            // the column's last chunk may run on into column L + 1
+            const uint32_t wq = sb + 4 * (ci1 - 1);
+            d16[ci1 - 1] = out4(w0, fbuf[M(wq + 1)], fbuf[M(wq + 2)], fbuf[M(wq + 3)], fbuf[M(wq + 4)]);
         }
         const uint32_t tb = a0 + 16 * n16 + (uint32_t)lane;
         if (tb < (uint32_t)fbytes) dst[tb] = byte_at(tb);
@@ -2864,7 +2870,11 @@ __device__ __forceinline__ void resolve_and_store(const EncodeParams &P, Pending
     // leave the bit buffer zeroed for this wave's next frame (LDS ops of one wave complete in order): the C rows
     // of the frame's matrix, or the whole buffer after a failed frame
     if (ok) {
-        for (uint32_t i = 0; i < M.c; i++) fbuf[(i << 6) | (uint32_t)lane] = 0;
+        // (the C rows are the buffer's first 64 C words: 16 C stores of 16 bytes, as in zero_wave_buf)
+        uint4 *b4 = reinterpret_cast<uint4 *>(fbuf);
+        const uint32_t n4 = M.c << 4;
+        for (uint32_t c = 0; c < n4; c += 64)
+            if (c + (uint32_t)lane < n4) b4[c + (uint32_t)lane] = make_uint4(0u, 0u, 0u, 0u);
     } else {
         for (uint32_t i = (uint32_t)lane; i < (uint32_t)kBufWordsV3; i += 64) fbuf[i] = 0;
     }
@@ -3250,6 +3260,10 @@ __device__ __forceinline__ void encode_frame_v4(const typename Elem<DT>::T *rast
                                                 int32_t *sub_est = nullptr) {
     using T = typename Elem<DT>::T;
     using Lane = std::conditional_t<WIDE, LaneWide, LanePairs>;
+    // (local: the lane predicates of the reductions and the field writers -- lane < 32, (lane & 7) == 0, ... -- are
+    // one v_cmp each; hoisted out of the ticket loop as 64-bit masks they are parked in VGPR lanes at 128 VGPRs and
+    // cost two v_readlane per use)
+    if constexpr (NW == 8) lane = (int)local_u32((uint32_t)lane);
     // (uni: a 1-D launch of 64 NW threads, so a wave's 64 threads share threadIdx.x >> 6)
     uint32_t *fbuf = S.bits[uni_if<!WIDE>(threadIdx.x >> 6)];  // holds the pending frame `prev` (or zero) on entry
     const int t = ftile[f];  // (f is wave-uniform, see k_encode_v4: the frame's tables are scalar loads)
