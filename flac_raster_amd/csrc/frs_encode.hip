@@ -34,6 +34,7 @@
 #include "frs_frame_header.h"
 #include "frs_crc16_fold.h"
 #include "frs_store_select.h"
+#include "frs_fixed_totals.h"
 
 namespace frs {
 
@@ -2881,52 +2882,6 @@ __device__ __forceinline__ void resolve_and_store(const EncodeParams &P, Pending
     pf.f = -1;
 }
 
-// fixed.c FLAC__fixed_compute_best_predictor, lane-parallel: this lane's sums of |e_k(i)|, k = 0..4, over its 64 samples
-// (packed pairs E[4 + m], E[2..3] = the previous lane's last four samples), lane 0 from sample 4 (tk); and lane 0's
-// terms at k <= i < 4 (hk: with tk, the fixed candidate's Rice sum from its warm-up on).  Differences are carried
-// sign-flipped (y = e ^ 2^31) so |e_{k+1}| = v_sad_u32(y_k(i), y_k(i-1)) in one op.
-__device__ inline void fixed_lane_totals(const uint32_t *E, bool l0, uint32_t *tk, uint32_t *hk) {
-    constexpr uint32_t M = 0x80000000u;
-    const int32_t h1 = (int32_t)E[3] >> 16, h2 = (int16_t)(E[3] & 0xFFFFu);
-    const int32_t h3 = (int32_t)E[2] >> 16, h4 = (int16_t)(E[2] & 0xFFFFu);
-    uint32_t p0 = (uint32_t)h1 ^ M, p1 = (uint32_t)(h1 - h2) ^ M, p2 = (uint32_t)((h1 - h2) - (h2 - h3)) ^ M;
-    uint32_t p3 = (uint32_t)(((h1 - h2) - (h2 - h3)) - ((h2 - h3) - (h3 - h4))) ^ M;
-    uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-#pragma unroll
-    for (int k = 0; k < 5; k++) hk[k] = 0;
-#pragma unroll
-    for (int j = 0; j < 64; j++) {
-        const uint32_t v = E[4 + (j >> 1)];
-        const int32_t x = (j & 1) ? ((int32_t)v >> 16) : (int32_t)(int16_t)(v & 0xFFFFu);
-        const uint32_t y0 = (uint32_t)x ^ M;
-        const uint32_t y1 = (y0 - p0) ^ M, y2 = (y1 - p1) ^ M, y3 = (y2 - p2) ^ M;
-        if (j < 4) {  // lane 0: not in the totals; its order-k terms from i = k are the Rice sum's
-            hk[0] = sad_u32(y0, M, hk[0]);
-            if (j >= 1) hk[1] = sad_u32(y0, p0, hk[1]);
-            if (j >= 2) hk[2] = sad_u32(y1, p1, hk[2]);
-            if (j >= 3) hk[3] = sad_u32(y2, p2, hk[3]);
-            if (!l0) {
-                t0 = sad_u32(y0, M, t0);
-                t1 = sad_u32(y0, p0, t1);
-                t2 = sad_u32(y1, p1, t2);
-                t3 = sad_u32(y2, p2, t3);
-                t4 = sad_u32(y3, p3, t4);
-            }
-        } else {
-            t0 = sad_u32(y0, M, t0);
-            t1 = sad_u32(y0, p0, t1);
-            t2 = sad_u32(y1, p1, t2);
-            t3 = sad_u32(y2, p2, t3);
-            t4 = sad_u32(y3, p3, t4);
-        }
-        p0 = y0;
-        p1 = y1;
-        p2 = y2;
-        p3 = y3;
-    }
-    tk[0] = t0, tk[1] = t1, tk[2] = t2, tk[3] = t3, tk[4] = t4;
-}
-
 // A lane's 64 consecutive samples of one coded signal, and the residual / fixed-predictor arithmetic on them.
 // LanePairs (16-bit signals): E[4 + m] = (x[2m], x[2m+1]) as int16 pairs, E[0..3] = the previous lane's last 8
 // samples (zeros on lane 0); LPC residuals by v_dot2 on packed pairs.  LaneWide (the 17-bit side signal of a
@@ -2948,7 +2903,8 @@ struct LanePairs {
         reg_fence(E);
     }
     __device__ inline void fence() { reg_fence(E); }
-    __device__ inline void totals(bool l0, uint32_t *tk, uint32_t *hk) const { fixed_lane_totals(E, l0, tk, hk); }
+    // fixed.c FLAC__fixed_compute_best_predictor, lane-parallel, on the packed pairs (frs_fixed_totals.h)
+    __device__ inline void totals(bool l0, uint32_t *tk, uint32_t *hk) const { frs::fixed_totals_pairs(E, l0, tk, hk); }
     __device__ inline uint32_t diff_from_first() const {  // OR of (x ^ x[0]) over the lane (wave-uniform x[0])
         const uint32_t x0 = uni(E[4] & 0xFFFFu);
         const uint32_t xx = x0 | (x0 << 16);

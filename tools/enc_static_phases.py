@@ -37,7 +37,6 @@ PHASES = [
     ("__device__ __forceinline__ void resolve_and_store(", "resolve/look-back"),
     ("        // ---- store [prefix, prefix + fbytes)", "store"),
     ("    // leave the bit buffer zeroed for this wave's next frame", "store (re-zeroing)"),
-    ("__device__ inline void fixed_lane_totals(", "totals"),
     ("struct LanePairs {", "lane samples (residuals, warm-up, history)"),
     ("__device__ __forceinline__ void rice_candidates(", "Rice search"),
     ("constexpr int kPrivRows", "assembly"),
@@ -52,7 +51,8 @@ PHASES = [
     ("template <int DT, bool SUB> constexpr int enc_nw()", "ticket loop"),
     ("// ---------------------------------------------------------------- multi-channel streams", "other"),
 ]
-BY_FILE = {"frs_crc16_fold.h": "CRC", "frs_frame_header.h": "header and fields", "frs_store_select.h": "store"}
+BY_FILE = {"frs_crc16_fold.h": "CRC", "frs_frame_header.h": "header and fields", "frs_store_select.h": "store",
+           "frs_fixed_totals.h": "totals"}
 
 
 def line_phases(src_text):
